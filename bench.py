@@ -13,9 +13,15 @@ Inputs are generated once and are resident in HBM before the timed region (SURVE
     python bench.py --gpus N --steps K --warmup W       # no launcher: bench.py starts the N ranks itself (child processes,
                                                         # before anything touches the GPU) and relays rank 0's JSON line
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed
-over the timed region) and `cpu_baseline` (the CPU oracle = validated port of the reference path, timed on the
-host cores in the same run, N=1 only).
+Rank 0 prints ONE JSON line (contract in the task statement): metric, value (clips/s), unit, higher_is_better, dtype,
+ms_per_step of the K timed steps.  A plain run does only that: set-up, W warm-up steps, K timed steps, the line.
+`--dump-outputs DIR` then also writes what the last timed step computed as DIR/<name>.npy (float32; inputs are seeded,
+so two builds run with the same arguments can be compared array by array).
+
+`--full` adds what takes time or runs of its own beyond the headline: HIP events around the staged entry points in the
+timed region, a second pass of K steps on one stream, `roofline` (dominant kernel) / `stages` / `kernel_ms_per_step`
+from them, the replica checksums of the collective (N > 1) and `cpu_baseline` (the CPU oracle = validated port of the
+reference path, timed on the host cores in the same run, N=1 only).
 """
 import argparse
 import json
@@ -42,10 +48,15 @@ def parse():
     ap.add_argument("--framesize", type=int, default=224)
     ap.add_argument("--fft_len", type=int, default=512)
     ap.add_argument("--hops_per_frame", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-event timing, the one-stream second pass (roofline, stages), the collective checksums (N > 1) "
+                         "and the CPU baseline (N = 1); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, a fixed sample of the large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true")
     ap.add_argument("--precise", action="store_true", help="exact-f32 MFMA in the fusion network (parity mode)")
-    ap.add_argument("--verbose", action="store_true", help="per-shape kernel table on stderr")
+    ap.add_argument("--verbose", action="store_true", help="per-shape kernel table on stderr (implies --full)")
     ap.add_argument("--vit-chunk", type=int, default=0, help="frames per ViT launch group (0 = library default)")
     ap.add_argument("--sync-bn", action="store_true", help="global-batch BatchNorm statistics over the ranks (N > 1)")
     ap.add_argument("--attn-dtype", choices=["same", "fp8", "fp8-late"], default="same",
@@ -66,7 +77,9 @@ def parse():
     ap.add_argument("--rank-echo", choices=["ok", "fail"], default=None, help=argparse.SUPPRESS)   # launcher self-test, no GPU work
     ap.add_argument("--vit-dtype", choices=["f16", "bf16"], default="f16",
                     help="16-bit storage / MFMA operand format of the ViT extractor (same MFMA rate; f16 meets the 1e-5 mask-MSE end to end)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.verbose
+    return args
 
 
 def synthetic_inputs(torch, batch, frames, width, length, seed, device):
@@ -130,6 +143,24 @@ def cpu_baseline(args):
                       f"the ViT, 85 % of the work, runs its {t} frames as one batch either way), whole clips: ViT-S/8 attention frames of all {t} {w}x{w} frames + "
                       f"{args.fft_len}-pt STFT + noise + AVSE fwd/bwd/Adam; {warm} warm-ups, median of {len(times)} timed clips "
                       f"({med:.2f} s/clip, min {min(times):.2f}, max {max(times):.2f})"}
+
+
+DUMP_MAX_ELEMS = 1 << 20      # per array (4 MB of float32): the eight arrays of --dump-outputs stay far below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy (float32) for every tensor of `arrays`.  An array of more than DUMP_MAX_ELEMS elements is written as a
+    fixed sample of its flattened elements (sorted indices from a generator of fixed seed: the same positions for the same
+    shape in every run and build)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(2024)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def lib_sha256():
@@ -272,7 +303,7 @@ def main():
         out = step_fn(x_stft, x_v, y_a, y_v)
         if pipe is not None and not serial:
             pipe.release()
-        return out
+        return out, (x_v, x_stft, y_stft)
 
     def sync_all():
         if world > 1:
@@ -282,15 +313,15 @@ def main():
     for i in range(args.warmup):
         step(i)
     sync_all()
-    # HIP events around the entry points the roofline / stage rows are made of (the ViT GEMMs and attention, STFT, Adam); with
-    # --verbose around every entry point (155 launches per step: the event pairs then cost ~0.9 ms of the step)
+    # --full: HIP events around the entry points the roofline / stage rows are made of (the ViT GEMMs and attention, STFT, Adam);
+    # with --verbose around every entry point (155 launches per step: the event pairs then cost ~0.9 ms of the step)
     staged = ("maavss_vit_attn", "maavss_vit_attn_mx", "maavss_vit_ws_gemm_ln_mx", "maavss_vit_panel_gemm", "maavss_vit_ws_gemm", "maavss_vit_ws_gemm_ln", "maavss_vit_ws_gemm_ln_post",
               "maavss_vit_gemm", "maavss_vit_gemm_stats", "maavss_stft_fwd", "maavss_adam_step")
-    timer = _lib.KernelTimer(only=None if args.verbose else staged)
+    timer = _lib.KernelTimer(only=None if args.verbose else staged) if args.full else None
     _lib.set_timer(timer)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        losses = step(args.warmup + i)
+        losses, batch = step(args.warmup + i)
     sync_all()
     elapsed = time.perf_counter() - t0
     _lib.set_timer(None)
@@ -299,10 +330,15 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = el.item()
     loss_val = float(losses[2].item())
-    # N > 1: evidence that the collective saw N ranks and kept the replicas identical -- every rank's parameter checksum
+    if args.dump_outputs and rank == 0:
+        x_v, x_stft, y_stft = batch
+        pred_audio, pred_video, fused = step_fn.outputs
+        dump_outputs(args.dump_outputs, {"loss": losses, "attention_frames": x_v, "x_stft": x_stft, "y_stft": y_stft, "pred_audio": pred_audio,
+                                         "pred_video": pred_video, "fused": fused, "params": step_fn.flat.params})
+    # N > 1, --full: evidence that the collective saw N ranks and kept the replicas identical -- every rank's parameter checksum
     # (f64 sum and sum of squares of the flat buffer after the K timed Adam steps), MIN- and MAX-reduced over the ranks
     collective = None
-    if world > 1:
+    if world > 1 and args.full:
         pf = step_fn.flat.params.double()
         cs = torch.stack([pf.sum(), (pf * pf).sum()])
         lo, hi = cs.clone(), cs.clone()
@@ -320,23 +356,24 @@ def main():
     if pipe is not None:
         pipe.drain()
     va.check_finite()                        # the deferred range flags of the last steps
-    # Second pass of K steps on ONE stream.  Pipelined run: with the HIP events -- a kernel's duration is only its own when
+    # --full: second pass of K steps on ONE stream.  Pipelined run: with the HIP events -- a kernel's duration is only its own when
     # it has the chip to itself, so the per-kernel roofline / stage rows come from this pass (the timed region above shares
     # the chip between the extractor's and the fusion network's kernels; its event times are reported next to them).
     # Serial run: without the events (transparency: what the events cost).
     timer_serial = None
-    if pipe is not None:
-        timer_serial = _lib.KernelTimer(only=None if args.verbose else staged)
-        _lib.set_timer(timer_serial)
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        step(args.warmup + args.steps + i, serial=True)
-    sync_all()
-    elapsed_second = time.perf_counter() - t1
-    _lib.set_timer(None)
-    va.check_finite()
+    if args.full:
+        if pipe is not None:
+            timer_serial = _lib.KernelTimer(only=None if args.verbose else staged)
+            _lib.set_timer(timer_serial)
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            step(args.warmup + args.steps + i, serial=True)
+        sync_all()
+        elapsed_second = time.perf_counter() - t1
+        _lib.set_timer(None)
+        va.check_finite()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         summ_timed = timer.summary()
         summ = timer_serial.summary() if timer_serial is not None else summ_timed
         # ---- roofline of the dominant kernel family (by accumulated HIP-event time)
@@ -490,6 +527,7 @@ def main():
                 print(f"[bench] {key}: {n} launches, {ms / n * 1e3:.1f} us avg, {fl / ms / 1e9:.0f} TFLOP/s", file=sys.stderr)
             print(f"[bench] sum of kernel time {sum(v['ms'] for v in summ.values()) / args.steps:.2f} ms/step, "
                   f"wall {(elapsed_second if timer_serial is not None else elapsed) / args.steps * 1e3:.2f} ms/step, {len(rec_timer.records) // args.steps} launches/step", file=sys.stderr)
+    if rank == 0:
         with open(os.path.join(ROOT, "BASELINE.json")) as fh:
             metric = json.load(fh)["metric"]
         clips = b * world * args.steps
@@ -498,7 +536,6 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32" if args.precise else args.vit_dtype, "data": "synthetic",
-            ("ms_per_step_one_stream" if pipe is not None else "ms_per_step_without_kernel_events"): round(elapsed_second / args.steps * 1e3, 3),
             "config": {"workload": f"batch={b}/GPU, {t} frames {w}x{w}, {args.fft_len}-pt STFT, ViT-S/8 attention extraction "
                                    f"({args.vit_dtype} MFMA operands, f32 accumulate) + STFT + AV_Fusion_Model_Frames fwd+bwd (16-bit MFMA conv, f32 accumulate) + Adam",
                        "global_batch": b * world, "frames": t, "framesize": w, "fft_len": args.fft_len,
@@ -510,16 +547,16 @@ def main():
                                                                     else ("3.0e-6 ... 6.5e-6 over five seed sets, shape P and the benched shape" if args.vit_dtype == "f16" else "2.3e-4 (shape P)") + " (tests/test_parity_r2_gpu.py, tests/test_parity_r3_gpu.py; target 1e-5)"),
                        "linear_lstm": "f32" + (" (deterministic: no atomic split-K)" if args.deterministic else " (split-K by f32 atomics)"), "batchnorm": "global-batch (sync)" if (args.sync_bn and world > 1) else "per-rank", "grad_all_reduce": f"{args.grad_wire} wire, per-module buckets in backward order",
                        "loss": loss_val},
-            "roofline": roofline,
-            "stages": stages,
-            "kernel_ms_per_step": breakdown,
         }
-        if timer_serial is not None:
-            out["kernel_ms_per_step_in_timed_region"] = {k: round(v["ms"] / args.steps, 3) for k, v in sorted(summ_timed.items(), key=lambda kv: -kv[1]["ms"])[:12]}
-        if collective is not None:
-            out["collective"] = collective
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args)
+        if args.full:
+            out["ms_per_step_one_stream" if pipe is not None else "ms_per_step_without_kernel_events"] = round(elapsed_second / args.steps * 1e3, 3)
+            out.update(roofline=roofline, stages=stages, kernel_ms_per_step=breakdown)
+            if timer_serial is not None:
+                out["kernel_ms_per_step_in_timed_region"] = {k: round(v["ms"] / args.steps, 3) for k, v in sorted(summ_timed.items(), key=lambda kv: -kv[1]["ms"])[:12]}
+            if collective is not None:
+                out["collective"] = collective
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -2,7 +2,7 @@
 # End-of-milestone evidence, run on the GPU box from the repo root (through gpurun):
 #   scripts/round_profiles.sh <tag>
 # writes into gpurun_out/ (copy the summaries into profiles/ afterwards):
-#   <tag>_bench.json               the default bench.py line (with cpu_baseline)
+#   <tag>_bench.json               the bench.py --full line (with roofline, stages and cpu_baseline)
 #   <tag>_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats of bench.py --pipeline off (one stream: a kernel's duration is its
 #                                  own, which is what the bench line's `roofline` reports from its one-stream pass)
 #   <tag>_bench_kernel_stats_two_streams.csv   the same for the default two-stream run (kernels share the chip: longer launches)
@@ -13,7 +13,7 @@ TAG=${1:-rX}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
-python3 $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 600 $OUT/${TAG}_bench.json; echo
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -- python3 $R/bench.py --pipeline off --steps 3 --warmup 1 --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1

@@ -82,16 +82,34 @@ def test_phasegram_variant_oracle_matches_reference_golden(golden_dir):
     assert abs(x_v.double().abs().sum().item() - z["pgram_abs_sum"]) < 1e-3
     x_a = torch.randn(b, 2, t_a, n_bins, generator=g) * 0.5
     y_a = torch.randn(b, 2, t_a, n_bins, generator=g) * 0.3
-    model.train()
+    # The fixture holds f32 results.  The network runs here in f64: an f32 rerun sums in another order on another host (thread
+    # count, vector width) and moved the most cancellation-prone gradient norm, phasegram_encoder.1.weight (4e-4 against up to
+    # 0.7), by 1.9e-4 of itself.  In f64 every gradient norm lands within 3e-6 of the fixture's, except that one: 1.04e-4, the
+    # fixture's own f32 rounding (4e-8) -- hence an absolute floor scaled by the largest gradient norm.
+    model = model.double().train()
+    x_v, x_a, y_a = x_v.double(), x_a.double(), y_a.double()
     yh_a, yh_v, fused = model(x_a, x_v)
     loss = torch.nn.functional.mse_loss(yh_v, x_v) + torch.nn.functional.mse_loss(yh_a, y_a)
     loss.backward()
     np.testing.assert_allclose(fused.detach().numpy(), z["full_fused"], rtol=1e-4, atol=2e-6)
     assert abs(loss.item() - z["full_loss"]) < 1e-6
     params = dict(model.named_parameters())
+    # A convolution bias directly in front of a train-mode BatchNorm has an exact gradient of zero: what the fixture holds for
+    # those (1e-9 ... 2e-6) is f32 rounding noise.  They must be zero up to rounding here (f64) and noise-sized in the fixture.
+    feeds_bn = set()
+    for name, mod in model.named_modules():
+        if isinstance(mod, torch.nn.Sequential):
+            kids = list(mod.named_children())
+            for (n0, m0), (_, m1) in zip(kids, kids[1:]):
+                if isinstance(m0, torch.nn.modules.conv._ConvNd) and m0.bias is not None and isinstance(m1, torch.nn.modules.batchnorm._BatchNorm):
+                    feeds_bn.add(f"{name}.{n0}.bias")
+    scale = float(np.max(z["full_grad_norm"]))
     for i, k in enumerate(z["full_param_names"]):
         gn = params[str(k)].grad.double().norm().item()
-        assert abs(gn - z["full_grad_norm"][i]) <= 1e-4 * z["full_grad_norm"][i] + 1e-9, k
+        if str(k) in feeds_bn:
+            assert z["full_grad_norm"][i] <= 1e-4 * scale and gn <= 1e-7 * scale, k
+        else:
+            assert abs(gn - z["full_grad_norm"][i]) <= 1e-4 * z["full_grad_norm"][i] + 1e-7 * scale, k
 
 
 def test_constructor_shapes_and_guards():
