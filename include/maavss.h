@@ -281,7 +281,7 @@ int maavss_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 int maavss_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 int maavss_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
 
-/* ---- K1-K6 DINO ViT-S/8 attention-frame extractor ------------------------------------------------
+/* ---- K1-K6 DINO ViT-S/8 and ViT-B/8 attention-frame extractor ---------------------------------------
  * What VideoAttention._inference (video_attention.py:38-103) obtains from dino's
  * VisionTransformer.get_last_selfattention (external module, call site video_attention.py:52), batched
  * over frames.  rows = frames * ntok, ntok = (H/8)*(W/8) + 1.
@@ -293,7 +293,7 @@ int maavss_bf16_to_f32(const void* src, float* dst, int64_t n, void* stream);
  * gemm     : C = epilogue(A[M][K] bf16 . W[N][K]^T bf16); N % 128 == 0, K % 64 == 0.  epilogue 0: +bias,
  *            columns < qscale_cols times qscale -> bf16;  1: +bias, exact GELU -> bf16;  2: C(f32) += acc + bias
  *            (residual, in place);  3: C(f32) = acc + table[row % period][N] (cls/pos-embed/conv-bias table).
- * layernorm: x [rows][384] f32 -> bf16 (eps as given, 1e-6 for DINO).
+ * layernorm: x [rows][dim] f32 -> bf16, dim 384 (ViT-S) or 768 (ViT-B) (eps as given, 1e-6 for DINO).
  * attn     : qkv [rows][ld_qkv] bf16 (q | k | v, heads x 64 each, q pre-scaled) -> out [rows][ld_out] bf16.
  * cls_attn : last block: softmax of the CLS query over all tokens, CLS column dropped -> att [F][heads][ntok-1] f32.
  * attn_maps: video_attention.py:80-96 + av_dataset.py:328: head sum, x(1/frame max), nearest x8 upsample,

@@ -1,7 +1,7 @@
 // K1 (patch gather), K2 (LayerNorm) and K6 (attention-map post-process) of the ViT attention extractor.
 //   vit_patchify      frames [F][3][H][W] f32 -> im2col rows [F*(n+1)][192] bf16 (row 0 of each frame = zeros for
 //                     the CLS slot; the GEMM's periodic row table adds cls_token / conv bias + position embedding)
-//   vit_layernorm     x [rows][384] f32 -> bf16, eps 1e-6, one wavefront per row (dino Block.norm1/norm2)
+//   vit_layernorm     x [rows][384 or 768] f32 -> bf16, eps 1e-6, one wavefront per row (dino Block.norm1/norm2)
 //   vit_attn_maps     reference video_attention.py:80-96 (reshape to [6,h,w], nearest x8 upsample, sum heads,
 //                     times 1/max per frame) and av_dataset.py:328 (times 1/max per clip), fused:
 //                     pass 1 per frame: head sum, frame max;  pass 2: clip max, upsampled store.
@@ -28,26 +28,30 @@ __global__ __launch_bounds__(256) void vit_patchify_kernel(const float* __restri
   }
 }
 
-template <int MODE>
+// DIM = 384 (ViT-S) or 768 (ViT-B): DIM / 128 float2 per lane (3 or 6, i.e. 6 or 12 values), lane-interleaved so that each
+// load instruction of the wave covers 512 contiguous bytes
+template <int DIM, int MODE>
 __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, bf16_t* __restrict__ y,
                                                             int64_t rows, float eps) {
+  static_assert(DIM % 128 == 0, "one wave per row, two values per lane and load");
+  constexpr int NV = DIM / 128;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float2* xp = reinterpret_cast<const float2*>(x + row * 384);
-  float2 v[3];
+  const float2* xp = reinterpret_cast<const float2*>(x + row * DIM);
+  float2 v[NV];
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < 3; ++i) { v[i] = xp[i * 64 + lane]; s += v[i].x + v[i].y; }
-  const float mean = wave_sum(s) * (1.f / 384.f);
+  for (int i = 0; i < NV; ++i) { v[i] = xp[i * 64 + lane]; s += v[i].x + v[i].y; }
+  const float mean = wave_sum(s) * (1.f / DIM);
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < 3; ++i) { const float a = v[i].x - mean, b = v[i].y - mean; q += a * a + b * b; }
-  const float rstd = rsqrtf(wave_sum(q) * (1.f / 384.f) + eps);
-  unsigned* yp = reinterpret_cast<unsigned*>(y + row * 384);
+  for (int i = 0; i < NV; ++i) { const float a = v[i].x - mean, b = v[i].y - mean; q += a * a + b * b; }
+  const float rstd = rsqrtf(wave_sum(q) * (1.f / DIM) + eps);
+  unsigned* yp = reinterpret_cast<unsigned*>(y + row * DIM);
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 2;
     yp[i * 64 + lane] = pack2<MODE>((v[i].x - mean) * rstd * gamma[c] + beta[c], (v[i].y - mean) * rstd * gamma[c + 1] + beta[c + 1]);
   }
@@ -156,11 +160,16 @@ extern "C" int maavss_vit_layernorm(const float* x, const float* gamma, const fl
                                     float eps, int dtype, void* stream) {
   MAAVSS_CHECK_ARG(x && gamma && beta && y && rows > 0, "vit_layernorm: bad arguments");
   MAAVSS_CHECK_ARG(dtype == 0 || dtype == 2, "vit_layernorm: dtype must be 0 (bf16) or 2 (f16)");
-  MAAVSS_CHECK_ARG(dim == 384, "vit_layernorm: only dim 384 (ViT-S) is built");
-  if (dtype == 2)
-    hipLaunchKernelGGL(vit_layernorm_kernel<2>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (bf16_t*)y, rows, eps);
-  else
-    hipLaunchKernelGGL(vit_layernorm_kernel<0>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (bf16_t*)y, rows, eps);
+  MAAVSS_CHECK_ARG(dim == 384 || dim == 768, "vit_layernorm: dim must be 384 (ViT-S) or 768 (ViT-B), got %d", dim);
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dim == 768) {
+    if (dtype == 2) hipLaunchKernelGGL((vit_layernorm_kernel<768, 2>), grid, block, 0, st, x, gamma, beta, (bf16_t*)y, rows, eps);
+    else hipLaunchKernelGGL((vit_layernorm_kernel<768, 0>), grid, block, 0, st, x, gamma, beta, (bf16_t*)y, rows, eps);
+  } else {
+    if (dtype == 2) hipLaunchKernelGGL((vit_layernorm_kernel<384, 2>), grid, block, 0, st, x, gamma, beta, (bf16_t*)y, rows, eps);
+    else hipLaunchKernelGGL((vit_layernorm_kernel<384, 0>), grid, block, 0, st, x, gamma, beta, (bf16_t*)y, rows, eps);
+  }
   MAAVSS_LAUNCH_CHECK("vit_layernorm_kernel");
   return MAAVSS_OK;
 }

@@ -7,8 +7,10 @@ per-clip normalisation of av_dataset.py:328.  The ViT-S/8 (dino.vision_transform
 num_classes=0), an un-vendored submodule of the reference) is restated from its published architecture:
 `self.model` is a plain state-dict holder with DINO's key names, so a DINO checkpoint
 (`dino_deitsmall8_pretrain.pth`, key "teacher", prefixes "module."/"backbone." stripped -- video_attention.py:
-116-129) loads unchanged.  There is no network in this environment: if the weights file is absent the
-extractor keeps its seeded random initialisation and says so (the reference would try to download).
+116-129) loads unchanged.  architecture="vit_base" builds DINO's other patch-8 backbone, ViT-B/8
+(`dino_vitbase8_pretrain.pth`: width 768, 12 heads, MLP 3072), on the width-generic kernels (`_cls_attention_generic`).
+There is no network in this environment: if the weights file is absent the extractor keeps its seeded random
+initialisation and says so (the reference would try to download).
 
 The dead sort/cumsum/threshold block of the reference (video_attention.py:59-78) never influences the
 returned frames and is not computed.
@@ -16,6 +18,7 @@ returned frames and is not computed.
 import math
 import os
 import sys
+from typing import NamedTuple
 
 import torch
 
@@ -30,29 +33,50 @@ DT_BF16, DT_F16 = 0, 2
 _TORCH_DT = {DT_BF16: torch.bfloat16, DT_F16: torch.float16}
 
 
-def vit_small_shapes(img_size=224):
+class ViTSpec(NamedTuple):
+    dim: int
+    heads: int
+    mlp: int
+    depth: int
+    checkpoint: str       # DINO's published file of this backbone at patch 8
+
+
+# The DINO patch-8 backbones the extractor builds.  vit_tiny (192 wide, 3 heads) is refused: DINO publishes no checkpoint for it,
+# and its widths 192 / 576 fall outside the N % 128 tiling of the generic GEMM.
+VIT_SPECS = {"vit_small": ViTSpec(DIM, HEADS, MLP, DEPTH, "dino_deitsmall8_pretrain.pth"),
+             "vit_base": ViTSpec(768, 12, 3072, 12, "dino_vitbase8_pretrain.pth")}
+
+
+def vit_shapes(architecture="vit_small", img_size=224):
+    """DINO state-dict keys and shapes of one backbone (pos_embed for img_size^2 frames)."""
+    d, _, mlp, depth, _ = VIT_SPECS[architecture]
     n = (img_size // PATCH) ** 2
-    sh = {"cls_token": (1, 1, DIM), "pos_embed": (1, n + 1, DIM),
-          "patch_embed.proj.weight": (DIM, 3, PATCH, PATCH), "patch_embed.proj.bias": (DIM,),
-          "norm.weight": (DIM,), "norm.bias": (DIM,)}
-    for i in range(DEPTH):
+    sh = {"cls_token": (1, 1, d), "pos_embed": (1, n + 1, d),
+          "patch_embed.proj.weight": (d, 3, PATCH, PATCH), "patch_embed.proj.bias": (d,),
+          "norm.weight": (d,), "norm.bias": (d,)}
+    for i in range(depth):
         p = f"blocks.{i}."
-        sh.update({p + "norm1.weight": (DIM,), p + "norm1.bias": (DIM,),
-                   p + "attn.qkv.weight": (3 * DIM, DIM), p + "attn.qkv.bias": (3 * DIM,),
-                   p + "attn.proj.weight": (DIM, DIM), p + "attn.proj.bias": (DIM,),
-                   p + "norm2.weight": (DIM,), p + "norm2.bias": (DIM,),
-                   p + "mlp.fc1.weight": (MLP, DIM), p + "mlp.fc1.bias": (MLP,),
-                   p + "mlp.fc2.weight": (DIM, MLP), p + "mlp.fc2.bias": (DIM,)})
+        sh.update({p + "norm1.weight": (d,), p + "norm1.bias": (d,),
+                   p + "attn.qkv.weight": (3 * d, d), p + "attn.qkv.bias": (3 * d,),
+                   p + "attn.proj.weight": (d, d), p + "attn.proj.bias": (d,),
+                   p + "norm2.weight": (d,), p + "norm2.bias": (d,),
+                   p + "mlp.fc1.weight": (mlp, d), p + "mlp.fc1.bias": (mlp,),
+                   p + "mlp.fc2.weight": (d, mlp), p + "mlp.fc2.bias": (d,)})
     return sh
 
 
-class ViTSmall8Weights:
-    """State-dict holder for the frozen ViT (the object the reference exposes as `VideoAttention.model`)."""
+def vit_small_shapes(img_size=224):
+    return vit_shapes("vit_small", img_size)
 
-    def __init__(self, seed=0):
+
+class DinoViTWeights:
+    """State-dict holder for the frozen ViT (the object the reference exposes as `VideoAttention.model`), DINO key names."""
+
+    def __init__(self, architecture="vit_small", seed=0):
+        self.architecture, self.spec = architecture, VIT_SPECS[architecture]
         g = torch.Generator().manual_seed(seed)
         self.sd = {}
-        for k, shape in vit_small_shapes().items():
+        for k, shape in vit_shapes(architecture).items():
             if k.endswith("norm1.weight") or k.endswith("norm2.weight") or k == "norm.weight":
                 t = torch.ones(shape)
             elif k.endswith(".bias"):
@@ -68,12 +92,23 @@ class ViTSmall8Weights:
     def load_state_dict(self, state_dict, strict=True):
         missing = [k for k in self.sd if k not in state_dict]
         unexpected = [k for k in state_dict if k not in self.sd]
+        width = next((int(state_dict[k].shape[-1]) for k in ("cls_token", "patch_embed.proj.bias") if k in state_dict), self.spec.dim)
+        if width != self.spec.dim:
+            # the common case: the reference's default path (dino_deitsmall8_pretrain.pth, width 384) under architecture="vit_base"
+            other = next((f" (a {a} checkpoint such as {s.checkpoint})" for a, s in VIT_SPECS.items() if s.dim == width), "")
+            raise RuntimeError(f"ViT checkpoint of width {width}{other} does not fit architecture={self.architecture!r}, which is "
+                               f"{self.spec.dim} wide: load {self.spec.checkpoint}")
         if strict and (missing or unexpected):
             raise RuntimeError(f"ViT state_dict mismatch: missing {missing[:4]}..., unexpected {unexpected[:4]}...")
         for k in self.sd:
             if k in state_dict:
                 t = torch.as_tensor(state_dict[k]).detach().float().cpu()
-                if k != "pos_embed" and tuple(t.shape) != tuple(self.sd[k].shape):
+                if k == "pos_embed":
+                    # any token count (interpolated per resolution), but a [1, n + 1, dim] table of this backbone's width
+                    if t.dim() != 3 or t.shape[0] != 1 or t.shape[2] != self.spec.dim:
+                        raise RuntimeError(f"pos_embed of shape {tuple(t.shape)} does not fit architecture={self.architecture!r}: "
+                                           f"expected [1, tokens, {self.spec.dim}]")
+                elif tuple(t.shape) != tuple(self.sd[k].shape):
                     raise RuntimeError(f"shape mismatch for {k}: {tuple(t.shape)} vs {tuple(self.sd[k].shape)}")
                 self.sd[k] = t.clone()
         return missing, unexpected
@@ -85,16 +120,21 @@ class ViTSmall8Weights:
         return self
 
 
+class ViTSmall8Weights(DinoViTWeights):
+    def __init__(self, seed=0):
+        super().__init__("vit_small", seed)
+
+
 def interpolate_pos_embed(pos_embed, h_tok, w_tok):
     """Host-side, once per resolution: DINO's bicubic resize of the patch position embedding (incl. its +0.1)."""
-    n = pos_embed.shape[1] - 1
+    n, d = pos_embed.shape[1] - 1, pos_embed.shape[2]
     if n == h_tok * w_tok and h_tok == w_tok:
         return pos_embed
     side = int(math.sqrt(n))
-    patch = pos_embed[:, 1:].reshape(1, side, side, DIM).permute(0, 3, 1, 2)
+    patch = pos_embed[:, 1:].reshape(1, side, side, d).permute(0, 3, 1, 2)
     patch = torch.nn.functional.interpolate(patch, scale_factor=((h_tok + 0.1) / side, (w_tok + 0.1) / side),
                                             mode="bicubic")
-    patch = patch.permute(0, 2, 3, 1).reshape(1, -1, DIM)
+    patch = patch.permute(0, 2, 3, 1).reshape(1, -1, d)
     return torch.cat([pos_embed[:, :1], patch], 1)
 
 
@@ -102,9 +142,28 @@ class VideoAttention:
     def __init__(self, patch_size=8, threshold=0.6, path_to_weights="dino_deitsmall8_pretrain.pth",
                  architecture="vit_small", resize=None, device="cuda", frames_per_launch=512, act_dtype="f16",
                  attn_dtype=None, fp8_blocks=None, gelu="f32", qkv_ln=None):
-        if patch_size != PATCH or architecture != "vit_small":
-            raise ValueError("only DINO vit_small / patch 8 is built (the configuration the reference uses, "
-                             "av_dataset.py:50)")
+        if patch_size != PATCH:
+            raise ValueError(f"patch_size={patch_size!r}: only DINO's patch-8 backbones are built (the reference uses patch 8, "
+                             "av_dataset.py:50; the patchify and attention-map kernels are specialised to 8x8 patches)")
+        if architecture == "vit_tiny":
+            raise ValueError("architecture='vit_tiny' is not built: DINO publishes no vit_tiny checkpoint, and its widths 192 / 576 fall "
+                             "outside the N % 128 tiling of the ViT GEMM")
+        if architecture not in VIT_SPECS:
+            raise ValueError(f"architecture={architecture!r}: choose one of {sorted(VIT_SPECS)}")
+        self.architecture, self.spec = architecture, VIT_SPECS[architecture]
+        if architecture != "vit_small":
+            # the fp8 attention images, the packed-half GELU and the gamma-folded qkv live in the weight-stationary K = 384 kernels
+            # (widths 384 / 1152 hard-wired): the other backbones run the width-generic kernels only
+            why = f"is built for vit_small only (its kernels are hard-wired to width 384 / 1152), not for architecture={architecture!r}"
+            if attn_dtype in ("fp8", "fp8-late"):
+                raise ValueError(f"attn_dtype={attn_dtype!r} {why}")
+            if fp8_blocks is not None:
+                raise ValueError(f"fp8_blocks {why}")
+            if gelu == "half":
+                raise ValueError(f"gelu='half' {why}")
+            if qkv_ln == "post":
+                raise ValueError(f"qkv_ln='post' {why}")
+            qkv_ln = "pre"           # the MAAVSS_QKV_LN environment default concerns the vit_small kernels only
         self.resize, self.threshold, self.patch_size = resize, threshold, patch_size
         # Keyword-only in spirit (not in the reference signature): storage format of weights and activations between the
         # kernels.  "f16" (default) = IEEE half: same MFMA rate as bf16, 8x smaller rounding error -- the difference
@@ -165,7 +224,7 @@ class VideoAttention:
         self._mx_ws = {}          # (rows, stream) -> zero-initialised workspace of the fp8 operand images (tails must stay zero); at most 4, LRU
 
     def __load_model(self, pretrained_weights):
-        model = ViTSmall8Weights()
+        model = ViTSmall8Weights() if self.architecture == "vit_small" else DinoViTWeights(self.architecture)
         if os.path.isfile(pretrained_weights):
             sd = torch.load(pretrained_weights, map_location="cpu", weights_only=True)
             if self.checkpoint_key is not None and self.checkpoint_key in sd:
@@ -189,8 +248,8 @@ class VideoAttention:
             sd, dev = self.model.sd, self.device
             bf = lambda t: t.to(dev).to(_TORCH_DT[self.dt]).contiguous()  # one-off dtype conversion of frozen weights
             f32 = lambda t: t.to(dev).float().contiguous()
-            d = {"patch_w": bf(sd["patch_embed.proj.weight"].reshape(DIM, 192))}
-            for i in range(DEPTH):
+            d = {"patch_w": bf(sd["patch_embed.proj.weight"].reshape(self.spec.dim, 192))}
+            for i in range(self.spec.depth):
                 p = f"blocks.{i}."
                 d[i] = dict(n1w=f32(sd[p + "norm1.weight"]), n1b=f32(sd[p + "norm1.bias"]),
                             qkv_w=bf(sd[p + "attn.qkv.weight"]), qkv_b=f32(sd[p + "attn.qkv.bias"]),
@@ -209,7 +268,7 @@ class VideoAttention:
         return self._dev
 
     def _row_table(self, h_tok, w_tok):
-        """[ntok][384] f32: row 0 = cls_token + pos[0]; row j = conv bias + pos[j] (prepare_tokens of DINO)."""
+        """[ntok][dim] f32: row 0 = cls_token + pos[0]; row j = conv bias + pos[j] (prepare_tokens of DINO)."""
         key = (h_tok, w_tok)
         if key not in self._tables:
             sd = self.model.sd
@@ -221,10 +280,13 @@ class VideoAttention:
 
     # ---- the ViT forward up to the last block's CLS attention ---------------------------------------
     def cls_attention(self, frames):
-        """frames [F,3,H,W] f32 cuda (H, W multiples of 8 are used) -> [F, 6, (H//8)*(W//8)] f32 cuda."""
+        """frames [F,3,H,W] f32 cuda (H, W multiples of 8 are used) -> [F, heads, (H//8)*(W//8)] f32 cuda (6 heads for vit_small,
+        12 for vit_base)."""
         _lib.require_cuda(frames)
         assert frames.dim() == 4 and frames.shape[1] == 3 and frames.dtype == torch.float32
         frames = frames.contiguous()
+        if self.architecture != "vit_small":
+            return self._cls_attention_generic(frames)
         f, _, h, w = frames.shape
         hp, wp = h // PATCH, w // PATCH
         ntok = hp * wp + 1
@@ -322,6 +384,48 @@ class VideoAttention:
         call("maavss_vit_cls_attn", ptr(qkv), ptr(att), f, ntok, HEADS, 3 * DIM, dt, st)
         return att
 
+    def _cls_attention_generic(self, frames):
+        """The block loop on the width-generic kernels (vit_base): LayerNorm passes of width dim, every dense layer on maavss_vit_gemm
+        (N % 128, K % 64), the flash attention and the CLS row with `heads` heads.  None of these kernels reads or writes a row past
+        M = frames * ntok (the GEMM clamps its A rows and guards its stores, the attention kernels clamp to the frame's last token),
+        so the buffers hold exactly the real rows."""
+        f, _, h, w = frames.shape
+        d, heads, mlp, depth, _ = self.spec
+        ntok = (h // PATCH) * (w // PATCH) + 1
+        rows = f * ntok
+        dev, st, dt, tdt = frames.device, stream_ptr(), self.dt, _TORCH_DT[self.dt]
+        wts, table = self._device_weights(), self._row_table(h // PATCH, w // PATCH)
+        a = torch.empty(rows, 192, device=dev, dtype=tdt)
+        x = torch.empty(rows, d, device=dev, dtype=torch.float32)            # residual stream
+        xn = torch.empty(rows, d, device=dev, dtype=tdt)
+        qkv = torch.empty(rows, 3 * d, device=dev, dtype=tdt)
+        att_o = torch.empty(rows, d, device=dev, dtype=tdt)
+        hid = torch.empty(rows, mlp, device=dev, dtype=tdt)
+        call("maavss_vit_patchify", ptr(frames), ptr(a), f, h, w, dt, st)
+        call("maavss_vit_gemm", ptr(a), 192, ptr(wts["patch_w"]), None, ptr(table), ntok, ptr(x), d, rows, d, 192,
+             EPI_F32_ROWTABLE, 0, 1.0, dt, st)
+        qs = 0.125 * 1.4426950408889634          # q *= log2(e)/sqrt(64): the attention kernels run softmax on exp2
+        for i in range(depth):
+            b = wts[i]
+            call("maavss_vit_layernorm", ptr(x), ptr(b["n1w"]), ptr(b["n1b"]), ptr(xn), rows, d, LN_EPS, dt, st)
+            # last block: q and k only (the CLS-row attention needs no v), into the same [rows, 3 d] buffer
+            nqkv = 2 * d if i == depth - 1 else 3 * d
+            call("maavss_vit_gemm", ptr(xn), d, ptr(b["qkv_w"]), ptr(b["qkv_b"]), None, 0, ptr(qkv), 3 * d, rows, nqkv, d,
+                 EPI_BF16_BIAS, d, qs, dt, st)
+            if i == depth - 1:
+                break
+            call("maavss_vit_attn", ptr(qkv), ptr(att_o), f, ntok, heads, 3 * d, d, dt, st)
+            call("maavss_vit_gemm", ptr(att_o), d, ptr(b["proj_w"]), ptr(b["proj_b"]), None, 0, ptr(x), d, rows, d, d,
+                 EPI_F32_BIAS_RESID, 0, 1.0, dt, st)
+            call("maavss_vit_layernorm", ptr(x), ptr(b["n2w"]), ptr(b["n2b"]), ptr(xn), rows, d, LN_EPS, dt, st)
+            call("maavss_vit_gemm", ptr(xn), d, ptr(b["fc1_w"]), ptr(b["fc1_b"]), None, 0, ptr(hid), mlp, rows, mlp, d,
+                 EPI_BF16_BIAS_GELU, 0, 1.0, dt, st)
+            call("maavss_vit_gemm", ptr(hid), mlp, ptr(b["fc2_w"]), ptr(b["fc2_b"]), None, 0, ptr(x), d, rows, d, mlp,
+                 EPI_F32_BIAS_RESID, 0, 1.0, dt, st)
+        att = torch.empty(f, heads, ntok - 1, device=dev, dtype=torch.float32)
+        call("maavss_vit_cls_attn", ptr(qkv), ptr(att), f, ntok, heads, 3 * d, dt, st)
+        return att
+
     def check_finite(self, wait=True):
         """Raise if an attention_frames(..., finite_check="deferred") call produced a non-finite CLS attention.  wait=True waits for
         the flag copies of all such calls (not for the device); wait=False looks only at copies that have already arrived."""
@@ -347,7 +451,7 @@ class VideoAttention:
         clip_frames = T additionally /clip max over consecutive groups of T frames, av_dataset.py:328;
         attn_diff=True first replaces each clip's frames by their temporal difference, av_dataset.py:323-326).
         Frames are processed `frames_per_launch` at a time (bounds the activation scratch: ~9.6 MB per frame at
-        224^2); measured on MI355X, fewer and larger launches win (512 frames/group: 75 ms/step vs 88 ms at 64).
+        224^2 for vit_small, ~13.6 MB for vit_base); measured on MI355X, fewer and larger launches win (512 frames/group: 75 ms/step vs 88 ms at 64).
 
         finite_check: the reference runs the ViT in fp32; here activations are stored in 16 bits and IEEE half (the default)
         overflows above 65504 -> inf -> NaN maps.  The maps kernel raises a sticky device flag when a CLS-attention value is
@@ -373,7 +477,7 @@ class VideoAttention:
             e = min(f, s + step)
             att = self.cls_attention(frames[s:e])
             ws = torch.empty((e - s) * (hp * wp + 1), device=frames.device, dtype=torch.float32)
-            call("maavss_vit_attn_maps_checked", ptr(att), ptr(out[s:e]), ptr(ws), e - s, HEADS, h, w, int(clip_frames),
+            call("maavss_vit_attn_maps_checked", ptr(att), ptr(out[s:e]), ptr(ws), e - s, self.spec.heads, h, w, int(clip_frames),
                  int(bool(attn_diff)), ptr(flag), stream_ptr())
         if flag is not None:
             if len(self._flag_pending) >= len(self._flag_hosts):
