@@ -7,6 +7,7 @@ stream (ClipPipeline).
 
     python examples/train_synthetic.py [--steps 6] [--batch 4] [--num_frames 8] [--num_seq 3] [--framesize 256]
     python examples/train_synthetic.py --overfit --steps 300 --lr 1e-4 --log_every 20     # one fixed batch: the loss has to fall
+    python examples/train_synthetic.py --raw_video 360x640 [--autocontrast]   # decoded uint8 clips through VideoTransform first
 """
 import argparse
 import os
@@ -32,6 +33,9 @@ def main():
     ap.add_argument("--overfit", action="store_true", help="train on ONE fixed batch (same clips, same noise draw) every step")
     ap.add_argument("--log_every", type=int, default=1)
     ap.add_argument("--precise", action="store_true", help="exact-f32 conv path instead of the 16-bit MFMA modes")
+    ap.add_argument("--raw_video", default=None, metavar="HxW",
+                    help="feed random uint8 HWC clips of this size through the GPU frame transform (RandomResizedCrop + Normalize)")
+    ap.add_argument("--autocontrast", action="store_true", help="with --raw_video: the reference's --autocontrast (run_config.py)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
@@ -43,12 +47,19 @@ def main():
     stft = maavss_amd.STFT(a.fft_len, hop, noise_std=0.1, device=dev)
     model = maavss_amd.AV_Fusion_Model_Frames([b, 2, hpf * nf, n_bins], [b, 1, nf, w, w], hpf, precise=a.precise).to(dev).train()
     step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns)
-    pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total)
+    transform = None
+    if a.raw_video:
+        h0, w0 = (int(v) for v in a.raw_video.lower().split("x"))
+        transform = maavss_amd.VideoTransform(w, autocontrast=a.autocontrast)
+    pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform)
 
     g = torch.Generator().manual_seed(0)
 
     def batch():
-        frames = torch.rand(b * t_total, 3, w, w, generator=g)
+        if transform is not None:
+            frames = torch.randint(0, 256, (b, t_total, h0, w0, 3), generator=g, dtype=torch.uint8)
+        else:
+            frames = torch.rand(b * t_total, 3, w, w, generator=g)
         audio = (0.3 * torch.randn(b, length, generator=g)).clamp(-1, 1)
         return frames.to(dev), audio.to(dev)
 

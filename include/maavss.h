@@ -384,6 +384,22 @@ int maavss_adaptive_pool_fwd(const float* x, float* out, int B, int H, int W, in
 int maavss_adaptive_pool_bwd(const float* dout, float* dx, int B, int H, int W, int C, int Ho, int Wo, int64_t os_b,
                              int64_t os_p, int64_t os_c, void* stream);
 
+/* ---- frame transform of the data path (no GPU form in the reference) ----------------------------------------------------
+ * AV_Dataset's clip transform (av_dataset.py:108-112 RandomResizedCrop(framesize, scale=(0.6, 1.0)) + Normalize, applied at
+ * av_dataset.py:315-319 and :346-350 after permute(0,3,1,2).float() / 255, followed by torchvision autocontrast when the
+ * dataset's `autocontrast` flag is set).  src uint8 [F][H0][W0][3] (the decoder's HWC frames); boxes int32 [F / clip_frames][4]
+ * = (top, left, height, width) on the DEVICE, one box shared by the clip_frames consecutive frames of a clip; host_boxes = the
+ * same values in host memory, checked (inside the frame, h, w >= 1) before any launch -- the kernels clamp to the frame as well.
+ * out f32 [F][3][S][S] = (interpolate(crop / 255, (S, S), bilinear, align_corners=False, antialias) - mean_c) / std_c, then with
+ * autocontrast = 1 per (frame, channel) plane (x - min) / (max - min) clamped to [0, 1] (a constant plane: clamp(x, 0, 1)).
+ * antialias = 1 is the separable triangle filter of torch's antialiased bilinear resize (support grows with the downscale
+ * factor, per axis).  S >= 8, a multiple of 4.  ws: maavss_video_transform_ws_bytes(...) bytes (16-byte aligned), or -1 when
+ * the arguments are invalid.  Additive in ABI 400. */
+int64_t maavss_video_transform_ws_bytes(int64_t F, int clip_frames, int H0, int W0, int S, int antialias, int autocontrast);
+int maavss_video_transform(const void* src, const int32_t* boxes, const int32_t* host_boxes, float* out, void* ws, int64_t ws_bytes,
+                           int64_t F, int clip_frames, int H0, int W0, int S, float mean0, float mean1, float mean2, float std0,
+                           float std1, float std2, int antialias, int autocontrast, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,25 +8,43 @@ next batch is enqueued on its own stream and joins the training stream through H
 fusion network's step (16 sequential LSTM launches per direction, the M = batch Linear layers, the small STFT-encoder
 convolutions) run next to the extractor's full-chip GEMMs instead of in front of them.  Slots are double-buffered; a slot
 is reused only after the training step that read it has been enqueued and has signalled its `consumed` event.
+
+With `transform` (a VideoTransform) the pipeline starts one stage earlier, at the decoder's uint8 clips: the frame transform of
+av_dataset.py:315-319 runs on the side stream in front of the extractor, into a per-slot frame buffer.
 """
 import torch
 
 
 class ClipPipeline:
-    def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred"):
+    def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None):
         self.va, self.stft, self.t = video_attention, stft, clip_frames
+        self.transform = transform
         self.depth = depth
         self.finite_check = finite_check
         self.side = torch.cuda.Stream()
         self.slots = [dict(attn=None, x=None, y=None, ready=torch.cuda.Event(), consumed=None) for _ in range(depth)]
+        if transform is not None:
+            for slot in self.slots:
+                slot["frames"] = None
         self.head = self.tail = 0            # next slot to submit into / next slot to hand out
 
-    def submit(self, frames, audio, seed):
+    def submit(self, frames, audio, seed, boxes=None):
         """Enqueue the extraction of one batch: frames [B*T,3,H,W], audio [B,L] (both resident on the device).  The caller's
-        stream must already hold the work that produced them (the side stream waits for it)."""
+        stream must already hold the work that produced them (the side stream waits for it).
+        With a transform, frames are the uint8 clips [B*T,H0,W0,3] or [B,T,H0,W0,3] and `boxes` the CPU crop boxes [B,4]; by default
+        transform.sample_boxes(B, H0, W0, torch.Generator().manual_seed(seed)), so a pipelined and a serial run see the same crops."""
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
         slot = self.slots[self.head % self.depth]
-        f, _, h, w = frames.shape
+        if self.transform is not None:
+            raw, _, boxes = self.transform.check(frames, boxes, self.t)      # everything is validated before any device work
+            f, h0, w0, _ = raw.shape
+            if boxes is None:
+                boxes = self.transform.sample_boxes(f // self.t, h0, w0, torch.Generator().manual_seed(seed))
+            h = w = self.transform.size
+        elif boxes is not None:
+            raise ValueError("boxes need a ClipPipeline built with transform=")
+        else:
+            f, _, h, w = frames.shape
         main = torch.cuda.current_stream()
         produced = torch.cuda.Event()
         produced.record(main)
@@ -39,6 +57,10 @@ class ClipPipeline:
                 self.side.wait_event(slot["consumed"])      # the training step that read this slot's buffers is past them
             if slot["attn"] is None or slot["attn"].shape != (f, 1, h, w):
                 slot["attn"] = torch.empty(f, 1, h, w, device=frames.device, dtype=torch.float32)
+            if self.transform is not None:
+                if slot["frames"] is None or slot["frames"].shape != (f, 3, h, w):
+                    slot["frames"] = torch.empty(f, 3, h, w, device=frames.device, dtype=torch.float32)
+                frames = self.transform(raw, boxes=boxes, clip_frames=self.t, out=slot["frames"])
             self.va.attention_frames(frames, clip_frames=self.t, out=slot["attn"], finite_check=self.finite_check)
             slot["x"], slot["y"] = self.stft(audio, seed=seed)    # replaces (frees) the tensors of two batches ago, after the wait above
             slot["ready"].record(self.side)
