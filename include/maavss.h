@@ -400,6 +400,36 @@ int maavss_video_transform(const void* src, const int32_t* boxes, const int32_t*
                            int64_t F, int clip_frames, int H0, int W0, int S, float mean0, float mean1, float mean2, float std0,
                            float std1, float std2, int antialias, int autocontrast, void* stream);
 
+/* ---- whole-recording inference (maavss_amd.Enhancer; train_avse_frames.py:139-176,196-200 done over every clip) --------------
+ * Pass 1 of maavss_vit_attn_maps_checked alone (video_attention.py:80-95): small [n_frames][n] = head sum of att [n_frames][heads][n]
+ * times 1 / its frame max, fmax [n_frames] = max of the scaled map, *nonfinite_flag as there.  The clip normalisation is left to
+ * the window gather, so the ViT runs once per recording frame, not once per (overlapping) clip.  Additive in ABI 400. */
+int maavss_vit_attn_maps_pass1(const float* att, float* small, float* fmax, int64_t n_frames, int heads, int n,
+                               int32_t* nonfinite_flag, void* stream);
+/* Per clip c of clip_frames frames from recording frame clip_start[c] (device int32 [n_clips], clamped into [0, n_frames -
+ * clip_frames]): clip_rcp[c] = 1 / (clip max) of av_dataset.py:328 -- over fmax (nullable; the pass-1 frame maxima) or else over
+ * the clip's maps [n_frames][frame_elems]; attn_diff = 1: over the zero-padded temporal difference, av_dataset.py:323-326. */
+int maavss_av_clip_scale(const float* maps, const float* fmax, const int32_t* clip_start, int64_t n_clips, int64_t n_frames,
+                         int clip_frames, int64_t frame_elems, int attn_diff, float* clip_rcp, void* stream);
+/* Attention windows of train_avse_frames.py:152 (x_attn[:, :, j:j+num_frames]) for windows w0 .. w0 + n_win - 1, window
+ * w = c * num_seq + j: out [n_win][win_frames][H][W] (16-byte aligned) = clip frames j .. j + win_frames - 1 of clip c, normalised
+ * as attention_frames(clip, clip_frames, attn_diff) does (bit for bit: same f32 operations).  upsample = 1: maps = pass-1 maps
+ * [n_frames][H/8][W/8], nearest x8 with zeros outside the patch grid (video_attention.py:80-96); 0: full-resolution maps
+ * [n_frames][H][W] (16-byte aligned), e.g. the reference's attention-frame cache (av_dataset.py:251-278). */
+int maavss_av_attn_windows(const float* maps, const float* clip_rcp, const int32_t* clip_start, int64_t n_clips, int64_t n_frames,
+                           int clip_frames, int num_seq, int win_frames, int64_t w0, int64_t n_win, int H, int W, int upsample,
+                           int attn_diff, float* out, void* stream);
+/* STFT windows of train_avse_frames.py:157-163: y [n_clips][2][clip_rows][n_bins] (one maavss_stft_fwd over overlapping rows) ->
+ * out [n_win][2][hops_per_frame * win_frames][n_bins], window w = c * num_seq + j = STFT frames hops_per_frame * j + [0, hops_per_frame *
+ * win_frames) of clip c. */
+int maavss_av_stft_windows(const float* y, int64_t n_clips, int clip_rows, int n_bins, int hops_per_frame, int num_seq, int win_frames,
+                           int64_t w0, int64_t n_win, float* out, void* stream);
+/* Stitch of train_avse_frames.py:172-174 over all clips: pred [n_win][2][hops_per_frame][n_bins] (the model's audio output) ->
+ * out [2][hops_per_frame * n_clips * num_seq][n_bins], rows hops_per_frame * w + [0, hops_per_frame) of window w = w0 + i = pred[i]
+ * times g_c = clip_absmax[c] + 1e-7 (the divisor of maavss_stft_normalise, av_dataset.py:339-340; clip_absmax null: g_c = 1). */
+int maavss_av_stitch(const float* pred, const float* clip_absmax, int64_t n_clips, int num_seq, int hops_per_frame, int n_bins,
+                     int64_t w0, int64_t n_win, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,3 +202,15 @@ extern "C" int maavss_vit_attn_maps(const float* att, float* out, float* ws, int
                                     int clip_frames, int attn_diff, void* stream) {
   return maavss_vit_attn_maps_checked(att, out, ws, n_frames, heads, H, W, clip_frames, attn_diff, nullptr, stream);
 }
+
+// pass 1 alone (maavss_amd.Enhancer: per-frame maps of a whole recording, cut into overlapping clips by maavss_av_attn_windows).
+// Reads n_frames * heads * n * 4 B, writes n_frames * (n + 1) * 4 B.
+extern "C" int maavss_vit_attn_maps_pass1(const float* att, float* small, float* fmax, int64_t n_frames, int heads, int n,
+                                          int32_t* nonfinite_flag, void* stream) {
+  MAAVSS_CHECK_ARG(att && small && fmax && n_frames > 0 && heads > 0 && n > 0, "vit_attn_maps_pass1: bad arguments");
+  MAAVSS_CHECK_ARG(n_frames <= 0x7fffffff, "vit_attn_maps_pass1: too many frames");
+  hipLaunchKernelGGL(vit_maps_pass1_kernel, dim3((unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, att, small, fmax, heads, n,
+                     nonfinite_flag);
+  MAAVSS_LAUNCH_CHECK("vit_maps_pass1_kernel");
+  return MAAVSS_OK;
+}

@@ -36,7 +36,10 @@ class STFT:
     def n_bins(self):
         return self.fft_len // 2 + (0 if self.trim_stft_end else 1)
 
-    def __call__(self, audio, noise=None, seed=0, want_x=True):
+    def __call__(self, audio, noise=None, seed=0, want_x=True, return_scale=False):
+        """-> (x_stft, y_stft), or with return_scale=True (x_stft, y_stft, amax): amax [B] = max |y| per clip before the
+        normalisation, which with `normalize_output_fft` divides y by amax + 1e-7 (av_dataset.py:339-340).  Rows of `audio`
+        may overlap (a row stride below L): maavss_amd.Enhancer cuts a recording into clips this way."""
         _lib.require_cuda(audio, noise)
         assert audio.dim() == 2 and audio.dtype == torch.float32 and audio.stride(1) == 1
         b, length = audio.shape
@@ -44,7 +47,7 @@ class STFT:
         f = self.n_bins()
         y = torch.empty(b, 2, n_frames, f, device=audio.device, dtype=torch.float32)
         x = torch.empty_like(y) if want_x else None
-        amax = torch.zeros(b, device=audio.device, dtype=torch.float32) if self.normalize_output_fft else None
+        amax = torch.zeros(b, device=audio.device, dtype=torch.float32) if (self.normalize_output_fft or return_scale) else None
         if noise is not None:
             assert noise.shape == y.shape and noise.is_contiguous() and noise.dtype == torch.float32
         st = _lib.stream_ptr()
@@ -55,7 +58,7 @@ class STFT:
         if self.normalize_output_fft:
             _lib.call("maavss_stft_normalise", _lib.ptr(y), _lib.ptr(x), _lib.ptr(noise), _lib.ptr(amax), b,
                       n_frames, f, float(self.noise_std), int(seed), st)
-        return x, y
+        return (x, y, amax) if return_scale else (x, y)
 
     def inverse(self, stft):
         """AV_Dataset.istft (av_dataset.py:181-201): [2, T_a, F] or [B, 2, T_a, F] (cuda) -> audio [hop*(T_a-1)] /
