@@ -151,12 +151,13 @@ def flash_attention_emulated(q, k, v, r):
     """softmax(q k^T) v of the flash kernel, rounding where it rounds: key tiles of 64 in order, a running maximum that
     only moves when a tile exceeds it by more than 2^5 (first tile: rebased to its own maximum), P = exp2(s - m) rounded
     to the 16-bit format for the P.V product while the row sum keeps the f32 values, O rescaled when m moves.
-    q (pre-scaled, log2 units), k, v: [b, heads, n, 64] f32 holding 16-bit-representable values."""
+    q (pre-scaled, log2 units), k, v: [b, heads, n, 64] f32 holding 16-bit-representable values; float64 inputs run the
+    whole recurrence in float64 (r then has to return float64 too), the kernel tests' exact reference."""
     n = k.shape[-2]
     s_all = q @ k.transpose(-2, -1)
-    m = torch.zeros(s_all.shape[:-1] + (1,))
+    m = torch.zeros(s_all.shape[:-1] + (1,), dtype=s_all.dtype)
     l = torch.zeros_like(m)
-    o = torch.zeros(q.shape)
+    o = torch.zeros(q.shape, dtype=s_all.dtype)
     for t0 in range(0, n, ATT_KT):
         s = s_all[..., t0:t0 + ATT_KT] - m
         mx = s.max(-1, keepdim=True).values

@@ -469,3 +469,50 @@ def test_convt2d_fwd_dgrad_wgrad_vs_torch(ci, co, kw, stride, opad, nhwc):
     np.testing.assert_allclose(dx.permute(0, 3, 1, 2).cpu().numpy(), x.grad.numpy(), rtol=1e-5, atol=2e-5)
     dw = ops.convt2d_wgrad(x_nhwc, dyc, w.shape, stride, opad, out_nhwc=nhwc)
     np.testing.assert_allclose(dw.cpu().numpy(), w.grad.numpy(), rtol=1e-4, atol=1e-4)
+
+
+# ----------------------------------------------------------------------------------------------- bf16 wire format
+def test_bf16_wire_conversion_is_bit_exact():
+    """maavss_f32_to_bf16 / maavss_bf16_to_f32 (the rounding step of GradSync(wire_dtype="bf16")) against torch's .bfloat16() /
+    .float(), bit for bit: exact ties with an even and an odd kept bit and one f32 ulp either side of them, +-0, f32 subnormals,
+    the largest finite f32 (rounds to inf), +-inf, NaNs (compared by isnan: payloads may differ; a NaN whose payload lies only in
+    the dropped bits must not become inf), and random bit patterns -- over a length past 4096 blocks x 256 threads x 8 elements,
+    so that the grid-stride loop wraps."""
+    from maavss_amd import ops
+    g = torch.Generator().manual_seed(17)
+    hi = torch.randint(0, 1 << 16, (4096,), generator=g, dtype=torch.int64) << 16
+    special = [hi | lo for lo in (0x8000, 0x7FFF, 0x8001)]                     # ties and one ulp either side, over random kept bits
+    special.append(((hi >> 17) << 17) | 0x8000)                                # ties with an even kept bit
+    special.append(((hi >> 17) << 17) | 0x18000)                               # ties with an odd kept bit
+    special.append(torch.randint(1, 1 << 23, (4096,), generator=g, dtype=torch.int64))          # f32 subnormals
+    special.append(torch.tensor([0x00008000, 0x00018000, 0x00007FFF, 0x007FFFFF, 0x00000001]))  # subnormal ties, largest subnormal
+    special.append(torch.tensor([0x00000000, 0x80000000, 0x7F7FFFFF, 0xFF7FFFFF, 0x7F7F8000, 0x7F800000, 0xFF800000,
+                                 0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7FFFFFFF, 0x7F808000]))
+    special = torch.cat(special)
+    special = torch.cat([special, special | (1 << 31)])                        # both signs
+    n = 4096 * 256 * 8 + 8 * 1234 + 8 * 3
+    bits = torch.randint(-(1 << 31), 1 << 31, (n,), generator=g, dtype=torch.int64)
+    pos = torch.randperm(n, generator=g)[:special.numel()]
+    bits[pos] = special
+    bits[n - special.numel():] = special                                       # and all of them again in the wrapped tail
+    src = bits.to(torch.int32).view(torch.float32)
+    want = src.bfloat16()
+    dst = torch.empty(n, dtype=torch.bfloat16, device="cuda")
+    ops.f32_to_bf16(src.cuda(), dst)
+    got = dst.cpu()
+    nan = torch.isnan(want)
+    assert torch.equal(torch.isnan(got), nan), "NaN-ness differs"
+    same = got.view(torch.int16) == want.view(torch.int16)
+    sub = (src.abs() < torch.finfo(torch.float32).tiny) & (src != 0)
+    print(f"[bf16 wire] {n} elements: {int((~same & ~nan).sum())} differ from torch, {int((~same & ~nan & sub).sum())} of them f32 subnormals "
+          f"({int(sub.sum())} subnormal inputs)")
+    assert bool((same | nan).all()), src[~(same | nan)][:8]
+    assert torch.isinf(got[src.abs() == torch.finfo(torch.float32).max]).all()
+    # widening: exact, NaN payloads included
+    wide = torch.empty(n, device="cuda")
+    ops.bf16_to_f32(want.cuda(), wide)
+    assert torch.equal(wide.cpu().view(torch.int32), want.float().view(torch.int32))
+    every = torch.arange(-(1 << 15), 1 << 15, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)        # all 65536 patterns
+    wide = torch.empty(every.numel(), device="cuda")
+    ops.bf16_to_f32(every.cuda(), wide)
+    assert torch.equal(wide.cpu().view(torch.int32), every.view(torch.int16).to(torch.int32) << 16)

@@ -1,7 +1,8 @@
 """VideoAttention(architecture="vit_base") -- DINO ViT-B/8 (width 768, 12 heads, MLP 3072) -- on the MI355X.
 
 Kernel level: the width-generic kernels at the ViT-B shapes against torch fp32 on the same 16-bit operands (the tolerances cover
-accumulation order and the 16-bit outputs).  End to end: the extractor against the CPU fp32 twin of DINO's ViT (tests/dino_twin.py),
+accumulation order and the 16-bit outputs), and each 16-bit output to one rounding of its float64 result (tests/rounding.py, its
+MIN_IDENTICAL fractions).  End to end: the extractor against the CPU fp32 twin of DINO's ViT (tests/dino_twin.py),
 with the gates tests/test_vit_gpu.py applies to the ViT-S/8 extractor."""
 import numpy as np
 import pytest
@@ -9,6 +10,8 @@ import torch
 import torch.nn.functional as F
 
 import dino_twin as tw
+from rounding import (MIN_IDENTICAL, U24, assert_attention_one_rounding, assert_cls_rows, assert_one_rounding, gelu_as64, gelu_as_budget,
+                      gemm_budget, layernorm64, layernorm_err)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,10 +62,17 @@ def test_vit_gemm_at_the_vit_base_shapes(layer, n, k, m, dt):
         got = c.float().cpu()
         np.testing.assert_allclose(got[:, :n].numpy(), want.numpy(), rtol=1e-2, atol=1e-2)
         assert (got[:, n:] == 7.0).all(), "columns past N were written"
+        v64, pb = a.double() @ w.double().t() + bias.double(), gemm_budget(a, w, bias)
+        qs = torch.where(torch.arange(n) < D, QS, 1.0).double()
+        assert_one_rounding(c[:, :n].cpu(), v64 * qs, DT[dt], budget64=(pb + U24 * v64.abs()) * qs + U24 * (v64 * qs).abs(),
+                            min_identical=MIN_IDENTICAL["gemm"], label=f"vit_gemm {layer} {m}x{n}x{k} dt {dt}")
     elif layer == "fc1":
         c = torch.empty(m, n, dtype=DT[dt], device="cuda")
         _call("maavss_vit_gemm", ac.data_ptr(), k, wc.data_ptr(), bc.data_ptr(), None, 0, c.data_ptr(), n, m, n, k, 1, 0, 1.0, dt, _st())
         np.testing.assert_allclose(c.float().cpu().numpy(), F.gelu(acc + bias).numpy(), rtol=1e-2, atol=1e-2)
+        v64 = a.double() @ w.double().t() + bias.double()
+        assert_one_rounding(c.cpu(), gelu_as64(v64), DT[dt], budget64=gelu_as_budget(v64, gemm_budget(a, w, bias)),
+                            min_identical=MIN_IDENTICAL["gelu_as"], label=f"vit_gemm fc1 (A-S GELU) {m}x{n}x{k} dt {dt}")
     else:
         # proj / fc2: epilogue 2, in place on the f32 residual stream; rows past M keep their contents
         res = rnd(m, n, seed=4)
@@ -85,6 +95,8 @@ def test_layernorm_768(dt):
     got = y.float().cpu()
     tol = 8e-3 if dt == 0 else 1e-3
     np.testing.assert_allclose(got[:rows].numpy(), want.numpy(), rtol=tol, atol=tol)
+    assert_one_rounding(y[:rows].cpu(), layernorm64(x, g, b)[0], DT[dt], budget64=layernorm_err(x, g, b), min_identical=MIN_IDENTICAL["ln_out"],
+                        label=f"vit_layernorm 768 dt {dt}")
     assert (got[rows:] == 3.0).all(), "rows past `rows` were written"
     with pytest.raises(Exception):                                       # widths other than 384 / 768 are refused
         _call("maavss_vit_layernorm", xc.data_ptr(), gc.data_ptr(), bc.data_ptr(), y.data_ptr(), rows, 512, 1e-6, dt, _st())
@@ -105,10 +117,12 @@ def test_attention_cls_row_and_maps_at_12_heads(ntok, frames, dt):
     want = (p @ v).transpose(1, 2).reshape(rows, D)
     tol = (2e-2, 8e-3) if dt == 0 else (3e-3, 1e-3)                      # P and O are rounded to the 16-bit format
     np.testing.assert_allclose(out.float().cpu().numpy(), want.numpy(), rtol=tol[0], atol=tol[1])
+    assert_attention_one_rounding(out, q, k, v, DT[dt], MIN_IDENTICAL["attn"], f"vit_attn 12 heads {ntok}x{frames} dt {dt}")
     att = torch.empty(frames, HEADS, ntok - 1, device="cuda")
     _call("maavss_vit_cls_attn", qc.data_ptr(), att.data_ptr(), frames, ntok, HEADS, 3 * D, dt, _st())
     cls = p[:, :, 0, 1:]
     np.testing.assert_allclose(att.cpu().numpy(), cls.numpy(), rtol=1e-3, atol=1e-7)
+    assert_cls_rows(att, q, k, f"vit_cls_attn 12 heads {ntok}x{frames} dt {dt}")
     # the 12-head sum of the maps kernel, on the f32 CLS rows just checked
     side = {785: (28, 28), 65: (8, 8)}[ntok]
     h, w = side[0] * 8, side[1] * 8

@@ -3,12 +3,17 @@
 The ViT has no reference oracle (dino is an empty submodule of the reference): the end-to-end
 check is against oracle/vit_ref_cpu.py (restated architecture, cross-checked against transformers.ViTModel in
 tests/test_oracle_cpu.py) -- "parity unpinned" to the reference itself.  Kernel-level checks feed the torch
-reference the SAME bf16-rounded operands, so their tolerances only cover accumulation order / bf16 outputs.
+reference the SAME bf16-rounded operands, so their tolerances only cover accumulation order / bf16 outputs.  On top of those, every
+16-bit output is held to one rounding of its float64 result (tests/rounding.py): within half an ulp + the kernel's f32 error
+budget everywhere, and bit-identical to the correctly rounded value in at least MIN_IDENTICAL of the elements.
 """
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from rounding import (MIN_IDENTICAL, U24, assert_attention_one_rounding, assert_cls_rows, assert_one_rounding, gelu_as64, gelu_as_budget,
+                      gelu_poly_budget, gemm_budget, layernorm64, layernorm_err, midpoint_slack, round16, stat_err)
 
 pytestmark = pytest.mark.gpu
 
@@ -50,9 +55,15 @@ def test_vit_gemm_epilogues(m, n, k, dt):
     want = z.clone()
     want[:, :384] *= 0.125
     np.testing.assert_allclose(c.float().cpu().numpy(), want.numpy(), rtol=1e-2, atol=1e-2)
+    v64, pb = a.double() @ w.double().t() + bias.double(), gemm_budget(a, w, bias)
+    qs = torch.where(torch.arange(n) < 384, 0.125, 1.0).double()      # a power of two: the scale itself is exact
+    assert_one_rounding(c.cpu(), v64 * qs, DT[dt], budget64=(pb + U24 * v64.abs()) * qs, min_identical=MIN_IDENTICAL["gemm"],
+                        label=f"vit_gemm epi 0 {m}x{n}x{k} dt {dt}")
     # 1: +bias, GELU -> bf16
     _call("maavss_vit_gemm", ac.data_ptr(), k, wc.data_ptr(), bc.data_ptr(), None, 0, c.data_ptr(), n, m, n, k, 1, 0, 1.0, dt, _st())
     np.testing.assert_allclose(c.float().cpu().numpy(), F.gelu(z).numpy(), rtol=1e-2, atol=1e-2)
+    assert_one_rounding(c.cpu(), gelu_as64(v64), DT[dt], budget64=gelu_as_budget(v64, pb), min_identical=MIN_IDENTICAL["gelu_as"],
+                        label=f"vit_gemm epi 1 (A-S GELU) {m}x{n}x{k} dt {dt}")
     # 2: residual in place, f32
     res = rnd(m, n, seed=4)
     x = res.clone().cuda()
@@ -89,6 +100,16 @@ def test_vit_gemm_f32_epilogue_stays_inside_its_rows_and_columns(epi):
     assert (got[:m, n:] == sentinel).all(), "columns past N were written"
 
 
+def _ln_gemm64(x, gam, bet, w, bias, dt16):
+    """LN64(x) rounded to the 16-bit format, then the product in float64; its budget: the f32 product's, plus -- where LN64 lies
+    within the f32 LayerNorm's error (layernorm_err) of a rounding midpoint, so that the kernel's operand may be the other
+    neighbour -- that ulp times |w|."""
+    y64 = layernorm64(x, gam, bet)[0]
+    xn = round16(y64, dt16)
+    slack = midpoint_slack(y64, dt16, layernorm_err(x, gam, bet))
+    return xn.double() @ w.double().t() + bias.double(), gemm_budget(xn, w, bias) + (slack.float() @ w.float().abs().t()).double()
+
+
 @pytest.mark.parametrize("dt", [0, 2])
 @pytest.mark.parametrize("m,n", [(1000, 1152), (785 * 2 + 3, 1536), (130, 384)])
 def test_vit_panel_gemm_fused_layernorm(m, n, dt):
@@ -107,9 +128,16 @@ def test_vit_panel_gemm_fused_layernorm(m, n, dt):
     want = z.clone()
     want[:, :384] *= 0.125
     np.testing.assert_allclose(c[:m].float().cpu().numpy(), want.numpy(), rtol=1.5e-2, atol=1.5e-2)
+    v64, pb = _ln_gemm64(x, gam, bet, w, bias, DT[dt])
+    qs = torch.where(torch.arange(n) < 384, 0.125, 1.0).double()
+    assert_one_rounding(c[:m].cpu(), v64 * qs, DT[dt], budget64=(pb + U24 * v64.abs()) * qs, min_identical=MIN_IDENTICAL["ln_gemm"],
+                        label=f"vit_panel_gemm LN epi 0 {m}x{n} dt {dt}")
     _call("maavss_vit_panel_gemm", xc.data_ptr(), None, 0, gc.data_ptr(), bc.data_ptr(), 1e-6, wc.data_ptr(), biasc.data_ptr(),
           c.data_ptr(), n, mp, m, n, 1, 0, 1.0, dt, _st())
     np.testing.assert_allclose(c[:m].float().cpu().numpy(), F.gelu(z).numpy(), rtol=1.5e-2, atol=1.5e-2)
+    from oracle import vit_ref_cpu as vref
+    assert_one_rounding(c[:m].cpu(), vref.gelu_poly(v64), DT[dt], budget64=gelu_poly_budget(v64, pb),
+                        min_identical=min(MIN_IDENTICAL["ln_gemm"], MIN_IDENTICAL["gelu_poly"]), label=f"vit_panel_gemm LN epi 1 (poly GELU) {m}x{n} dt {dt}")
     # bf16 input (no LayerNorm), f32 residual in place
     a = rd(rnd(m, k, seed=6), dt)
     res = rnd(m, n, seed=7)
@@ -122,6 +150,15 @@ def test_vit_panel_gemm_fused_layernorm(m, n, dt):
     with pytest.raises(Exception):                     # unpadded output is refused
         _call("maavss_vit_panel_gemm", None, ac.data_ptr(), k, None, None, 1e-6, wc.data_ptr(), biasc.data_ptr(), rc.data_ptr(), n,
               m - 1 if m % 128 == 0 else m, m, n, 2, 0, 1.0, dt, _st())
+
+
+def _ln_input_err(x64, dx, gam=None):
+    """How far LayerNorm's output moves when its input row moves by at most dx elementwise: gamma rstd (dx_i + max dx) through the
+    centring, and gamma xhat rstd max dx through rstd (|d var| <= 2 std max dx, so |d rstd| / rstd <= rstd max dx)."""
+    _, xhat, rstd = layernorm64(x64)
+    g = gam.double().abs() if gam is not None else 1.0
+    dmax = dx.amax(-1, keepdim=True)
+    return g * rstd * (dx + dmax + xhat.abs() * dmax)
 
 
 @pytest.mark.parametrize("dt", [0, 2])
@@ -145,9 +182,16 @@ def test_vit_ws_gemm(m, n, dt):
     want = z.clone()
     want[:, :384] *= 0.125
     np.testing.assert_allclose(c[:m].float().cpu().numpy(), want.numpy(), rtol=1.5e-2, atol=1.5e-2)
+    v64, pb = a.double() @ w.double().t() + bias.double(), gemm_budget(a, w, bias)
+    qs = torch.where(torch.arange(n) < 384, 0.125, 1.0).double()
+    assert_one_rounding(c[:m].cpu(), v64 * qs, DT[dt], budget64=(pb + U24 * v64.abs()) * qs, min_identical=MIN_IDENTICAL["gemm"],
+                        label=f"vit_ws_gemm epi 0 {m}x{n} dt {dt}")
     _call("maavss_vit_ws_gemm", ac.data_ptr(), k, mp, wc.data_ptr(), biasc.data_ptr(), c.data_ptr(), n, mp, m, n, 1, 0, 1.0,
           None, None, None, 1e-6, dt, _st())
     np.testing.assert_allclose(c[:m].float().cpu().numpy(), F.gelu(z).numpy(), rtol=1.5e-2, atol=1.5e-2)
+    from oracle import vit_ref_cpu as vref
+    assert_one_rounding(c[:m].cpu(), vref.gelu_poly(v64), DT[dt], budget64=gelu_poly_budget(v64, pb), min_identical=MIN_IDENTICAL["gelu_poly"],
+                        label=f"vit_ws_gemm epi 1 (poly GELU) {m}x{n} dt {dt}")
     res = rnd(m, n, seed=7)
     rc = torch.zeros(mp, n, device="cuda")
     rc[:m] = res.cuda()
@@ -163,11 +207,17 @@ def test_vit_ws_gemm(m, n, dt):
               xn.data_ptr(), gc.data_ptr(), bc.data_ptr(), 1e-6, dt, _st())
         np.testing.assert_allclose(rc[:m].cpu().numpy(), (res + z).numpy(), rtol=1e-4, atol=3e-4)
         np.testing.assert_allclose(xn[:m].float().cpu().numpy(), F.layer_norm(res + z, (k,), gam, bet, 1e-6).numpy(), rtol=8e-3, atol=8e-3)
+        x64 = res.double() + v64                # the updated row, whose f32 value the kernel normalises
+        dx = pb + U24 * x64.abs()               # ... off by the product's budget and the residual add
+        assert_one_rounding(xn[:m].cpu(), layernorm64(x64, gam, bet)[0], DT[dt], budget64=_ln_input_err(x64, dx, gam) + layernorm_err(x64, gam, bet),
+                            min_identical=MIN_IDENTICAL["ln_out"], label=f"vit_ws_gemm epi 2 xn {m}x{n} dt {dt}")
         rc[:m] = res.cuda()                 # NULL gamma / beta: the plain normalised rows
         _call("maavss_vit_ws_gemm", ac.data_ptr(), k, mp, wc.data_ptr(), biasc.data_ptr(), rc.data_ptr(), n, mp, m, n, 2, 0, 1.0,
               xn.data_ptr(), None, None, 1e-6, dt, _st())
         np.testing.assert_allclose(rc[:m].cpu().numpy(), (res + z).numpy(), rtol=1e-4, atol=3e-4)
         np.testing.assert_allclose(xn[:m].float().cpu().numpy(), F.layer_norm(res + z, (k,), None, None, 1e-6).numpy(), rtol=8e-3, atol=8e-3)
+        assert_one_rounding(xn[:m].cpu(), layernorm64(x64)[0], DT[dt], budget64=_ln_input_err(x64, dx) + layernorm_err(x64),
+                            min_identical=MIN_IDENTICAL["ln_out"], label=f"vit_ws_gemm epi 2 xn (no affine) {m}x{n} dt {dt}")
     with pytest.raises(Exception):                     # unpadded buffers are refused
         _call("maavss_vit_ws_gemm", ac.data_ptr(), k, mp, wc.data_ptr(), biasc.data_ptr(), rc.data_ptr(), n, m - 1 if m % 64 == 0 else m,
               m, n, 2, 0, 1.0, None, None, None, 1e-6, dt, _st())
@@ -239,6 +289,10 @@ def test_vit_ws_gemm_with_layernorm_on_the_way_in(m, n, dt):
     _call("maavss_vit_ws_gemm_ln", xc.data_ptr(), mp, stats.data_ptr(), gc.data_ptr(), bc.data_ptr(), 1e-6, wc.data_ptr(), biasc.data_ptr(),
           c.data_ptr(), n, mp, m, n, 384, 0.125, dt, _st())
     np.testing.assert_allclose(c[:m].float().cpu().numpy(), want.numpy(), rtol=1.5e-2, atol=1.5e-2)
+    qs = torch.where(torch.arange(n) < 384, 0.125, 1.0).double()
+    v64, pb = _ln_gemm64(x, gam, bet, w, bias, DT[dt])
+    assert_one_rounding(c[:m].cpu(), v64 * qs, DT[dt], budget64=(pb + U24 * v64.abs()) * qs, min_identical=MIN_IDENTICAL["ln_gemm"],
+                        label=f"vit_ws_gemm_ln {m}x{n} dt {dt}")
     # NULL gamma / beta = the LayerNorm without its affine part (round 4: VideoAttention folds gamma / beta into the frozen weights): bit-identical
     # to gamma = 1, beta = 0, and with the folded weights W diag(gamma), b + W beta the same result as above up to the two roundings' order
     ones, zeros = torch.ones(k, device="cuda"), torch.zeros(k, device="cuda")
@@ -257,6 +311,9 @@ def test_vit_ws_gemm_with_layernorm_on_the_way_in(m, n, dt):
     want_f = xhat @ wf.float().t() + bf_
     want_f[:, :384] *= 0.125
     np.testing.assert_allclose(c0[:m].float().cpu().numpy(), want_f.numpy(), rtol=1.5e-2, atol=1.5e-2)
+    v64, pb = _ln_gemm64(x, None, None, wf, bf_, DT[dt])
+    assert_one_rounding(c0[:m].cpu(), v64 * qs, DT[dt], budget64=(pb + U24 * v64.abs()) * qs, min_identical=MIN_IDENTICAL["ln_gemm"],
+                        label=f"vit_ws_gemm_ln folded weights {m}x{n} dt {dt}")
     np.testing.assert_allclose(c0[:m].float().cpu().numpy(), want.numpy(), rtol=3e-2, atol=3e-2)
     with pytest.raises(Exception, match="both given or both null"):
         _call("maavss_vit_ws_gemm_ln", xc.data_ptr(), mp, stats.data_ptr(), gc.data_ptr(), None, 1e-6, wc.data_ptr(), biasc.data_ptr(),
@@ -273,6 +330,17 @@ def test_vit_ws_gemm_with_layernorm_on_the_way_in(m, n, dt):
     want_p = rstd * (rd(x, dt).float() @ wf.float().t() - mu * cs[None, :]) + bf_
     want_p[:, :384] *= 0.125
     np.testing.assert_allclose(cp[:m].float().cpu().numpy(), want_p.numpy(), rtol=1.5e-2, atol=1.5e-2)
+    # want_p in float64.  Budget: the product x W'^T - mean s (the accumulator starts at -mean s) times rstd; the kernel's f32 mean
+    # (off by stat_err(K) mean|x|) times rstd |s|; its f32 rstd (off by stat_err(K) / 2 + 2 ulp relative) times |the result|; the fma with b'
+    xr, rstd64 = rd(x, dt), layernorm64(x)[2]
+    mu64 = x.double().mean(-1, keepdim=True)
+    acc64 = xr.double() @ wf.double().t() - mu64 * cs.double()
+    p64 = rstd64 * acc64 + bf_.double()
+    dmu = stat_err(k) * x.double().abs().mean(-1, keepdim=True)
+    pb = rstd64 * (gemm_budget(xr, wf) + stat_err(k) * (mu64 * cs.double()).abs() + dmu * cs.double().abs()) \
+        + (0.5 * stat_err(k) + 2 * U24) * (rstd64 * acc64).abs() + U24 * p64.abs()
+    assert_one_rounding(cp[:m].cpu(), p64 * qs, DT[dt], budget64=pb * qs, min_identical=MIN_IDENTICAL["ln_gemm"],
+                        label=f"vit_ws_gemm_ln_post {m}x{n} dt {dt}")
     np.testing.assert_allclose(cp[:m].float().cpu().numpy(), want.numpy(), rtol=4e-2, atol=4e-2)
 
 
@@ -284,6 +352,8 @@ def test_vit_layernorm_and_patchify():
     _call("maavss_vit_layernorm", xc.data_ptr(), gc.data_ptr(), bc.data_ptr(), y.data_ptr(), rows, 384, 1e-6, 0, _st())
     want = F.layer_norm(x, (384,), g, b, 1e-6)
     np.testing.assert_allclose(y.float().cpu().numpy(), want.numpy(), rtol=8e-3, atol=8e-3)
+    y64, lerr = layernorm64(x, g, b)[0], layernorm_err(x, g, b)
+    assert_one_rounding(y.cpu(), y64, torch.bfloat16, budget64=lerr, min_identical=MIN_IDENTICAL["ln_out"], label="vit_layernorm 384 bf16")
     fr = rnd(3, 3, 40, 24, seed=4)
     ntok = 5 * 3 + 1
     a = torch.empty(3 * ntok, 192, dtype=torch.bfloat16, device="cuda")
@@ -299,6 +369,7 @@ def test_vit_layernorm_and_patchify():
     yh = torch.empty(rows, 384, dtype=torch.float16, device="cuda")
     _call("maavss_vit_layernorm", xc.data_ptr(), gc.data_ptr(), bc.data_ptr(), yh.data_ptr(), rows, 384, 1e-6, 2, _st())
     np.testing.assert_allclose(yh.float().cpu().numpy(), F.layer_norm(x, (384,), g, b, 1e-6).numpy(), rtol=1e-3, atol=1e-3)
+    assert_one_rounding(yh.cpu(), y64, torch.float16, budget64=lerr, min_identical=MIN_IDENTICAL["ln_out"], label="vit_layernorm 384 f16")
 
 
 @pytest.mark.parametrize("dt", [0, 2])
@@ -318,9 +389,11 @@ def test_vit_attention_and_cls(ntok, frames, dt):
     want = (p @ v).transpose(1, 2).reshape(rows, 384)
     tol = (2e-2, 8e-3) if dt == 0 else (3e-3, 1e-3)              # P and O are rounded to the 16-bit format
     np.testing.assert_allclose(out.float().cpu().numpy(), want.numpy(), rtol=tol[0], atol=tol[1])
+    assert_attention_one_rounding(out, q, k, v, DT[dt], MIN_IDENTICAL["attn"], f"vit_attn {ntok}x{frames} dt {dt}")
     att = torch.empty(frames, 6, ntok - 1, device="cuda")
     _call("maavss_vit_cls_attn", qc.data_ptr(), att.data_ptr(), frames, ntok, 6, 1152, dt, _st())
     np.testing.assert_allclose(att.cpu().numpy(), p[:, :, 0, 1:].numpy(), rtol=1e-3, atol=1e-7)
+    assert_cls_rows(att, q, k, f"vit_cls_attn {ntok}x{frames} dt {dt}")
 
 
 @pytest.mark.parametrize("dt", [0, 2])
@@ -347,6 +420,7 @@ def test_vit_attention_edges_and_running_maximum(ntok, frames, ramp, dt):
     got = out.double().cpu()
     assert torch.isfinite(got).all()
     np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=2e-2, atol=1.2e-2)
+    assert_attention_one_rounding(out, q, k, v, DT[dt], MIN_IDENTICAL["attn"], f"vit_attn edges {ntok}x{frames} ramp {ramp} dt {dt}")
 
 
 def _fp8(x):
