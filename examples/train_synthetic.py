@@ -8,6 +8,7 @@ stream (ClipPipeline).
     python examples/train_synthetic.py [--steps 6] [--batch 4] [--num_frames 8] [--num_seq 3] [--framesize 256]
     python examples/train_synthetic.py --overfit --steps 300 --lr 1e-4 --log_every 20     # one fixed batch: the loss has to fall
     python examples/train_synthetic.py --raw_video 360x640 [--autocontrast]   # decoded uint8 clips through VideoTransform first
+    python examples/train_synthetic.py --raw_audio [--compress_audio]         # 44.1 kHz stereo int16 clips through AudioTransform first
 """
 import argparse
 import os
@@ -36,6 +37,9 @@ def main():
     ap.add_argument("--raw_video", default=None, metavar="HxW",
                     help="feed random uint8 HWC clips of this size through the GPU frame transform (RandomResizedCrop + Normalize)")
     ap.add_argument("--autocontrast", action="store_true", help="with --raw_video: the reference's --autocontrast (run_config.py)")
+    ap.add_argument("--raw_audio", action="store_true",
+                    help="feed 44.1 kHz stereo int16 clips through the GPU audio transform (downmix + resampling to 16 kHz)")
+    ap.add_argument("--compress_audio", action="store_true", help="with --raw_audio: the reference's --compress_audio (run_config.py)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
@@ -51,7 +55,12 @@ def main():
     if a.raw_video:
         h0, w0 = (int(v) for v in a.raw_video.lower().split("x"))
         transform = maavss_amd.VideoTransform(w, autocontrast=a.autocontrast)
-    pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform)
+    audio_transform, raw_sr = None, 44100
+    if a.raw_audio:
+        audio_transform = maavss_amd.AudioTransform(16000, compress_audio=a.compress_audio)
+        raw_length = audio_transform.input_length(length, raw_sr)      # the fewest 44.1 kHz samples that give `length` at 16 kHz
+    pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform, audio_transform=audio_transform,
+                                   audio_length=length if a.raw_audio else None)
 
     g = torch.Generator().manual_seed(0)
 
@@ -60,13 +69,17 @@ def main():
             frames = torch.randint(0, 256, (b, t_total, h0, w0, 3), generator=g, dtype=torch.uint8)
         else:
             frames = torch.rand(b * t_total, 3, w, w, generator=g)
-        audio = (0.3 * torch.randn(b, length, generator=g)).clamp(-1, 1)
+        if audio_transform is not None:
+            audio = (0.3 * 32767 * torch.randn(b, 2, raw_length, generator=g)).clamp(-32768, 32767).to(torch.int16)
+        else:
+            audio = (0.3 * torch.randn(b, length, generator=g)).clamp(-1, 1)
         return frames.to(dev), audio.to(dev)
 
     fixed = batch() if a.overfit else None
-    pipe.submit(*(fixed or batch()), seed=0)
+    sr_arg = dict(audio_sr=raw_sr) if a.raw_audio else {}
+    pipe.submit(*(fixed or batch()), seed=0, **sr_arg)
     for i in range(a.steps):
-        pipe.submit(*(fixed or batch()), seed=0 if a.overfit else i + 1)      # extraction of the next batch: side stream
+        pipe.submit(*(fixed or batch()), seed=0 if a.overfit else i + 1, **sr_arg)      # extraction of the next batch: side stream
         attn, x_stft, y_stft = pipe.get()                        # [B,1,T,H,W], [B,2,T_a,F] x 2
         losses = step.sliding_window_step(x_stft, y_stft, attn, attn, nf, hpf)
         pipe.release()

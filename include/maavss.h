@@ -400,6 +400,27 @@ int maavss_video_transform(const void* src, const int32_t* boxes, const int32_t*
                            int64_t F, int clip_frames, int H0, int W0, int S, float mean0, float mean1, float mean2, float std0,
                            float std1, float std2, int antialias, int autocontrast, void* stream);
 
+/* ---- audio transform of the data path (no GPU form in the reference) ----------------------------------------------------------
+ * AV_Dataset.audio_transforms (av_dataset.py:203-215): channel downmix (every channel / C, summed in channel order), with
+ * normalize = 1 the clip TIMES its own max |x| (av_dataset.py:209 as written), torchaudio's sinc_interp_hann Resample(orig -> new)
+ * and with contrast = 1 torchaudio.functional.contrast(x, 75) = sin(x pi/2 + 0.1 sin(4 x pi/2)).
+ * src [B][C][L0] addressed b * stride_b + c * stride_c + i (elements); src_dtype 0 = f32, 1 = int16 (scaled by 2^-15).
+ * orig_rate, new_rate: the two rates divided by their gcd.  orig_rate == new_rate: no resampling (taps / first_tap may be null, L <= L0),
+ * samples pass through unchanged.  Otherwise the COMPRESSED polyphase table of the host (maavss_amd/audio_transform.py): taps f32
+ * [S][new_rate] (tap-major), taps[k][p] = dense tap first_tap[p] + k of phase p, first_tap int32 [new_rate]; `width` as torchaudio
+ * defines it (ceil(lowpass_filter_width * orig / base)).  The signal is zero-padded; output n = j * new_rate + p of a clip is
+ * sum_k taps[k][p] * x[j * orig_rate - width + first_tap[p] + k], k ascending in one f32 FMA chain.  first_tap must be the first tap of
+ * the window's support (floor(a + p * orig / new) + 1 for one a): the kernel stages ceil(255 orig / new) + S + 2 input samples per 256
+ * outputs and clamps every read into them, so another table gives wrong samples but no access out of bounds; that span is limited to
+ * 16384 samples (orig / new up to about 60) and new_rate * S to 2^22.
+ * out f32, row b at out + b * ld_out, L <= ceil(new_rate * L0 / orig_rate) samples per clip (a shorter L crops).
+ * ws: maavss_audio_transform_ws_bytes(...) bytes (0 without normalize: ws may then be null), -1 when the arguments are invalid.
+ * At most two launches (one without normalize).  Additive in ABI 400. */
+int64_t maavss_audio_transform_ws_bytes(int64_t B, int C, int64_t L0, int normalize);
+int maavss_audio_transform(const void* src, int src_dtype, int64_t B, int C, int64_t L0, int64_t stride_b, int64_t stride_c,
+                           const float* taps, const int32_t* first_tap, int orig_rate, int new_rate, int S, int width, int normalize,
+                           int contrast, float* out, int64_t L, int64_t ld_out, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- whole-recording inference (maavss_amd.Enhancer; train_avse_frames.py:139-176,196-200 done over every clip) --------------
  * Pass 1 of maavss_vit_attn_maps_checked alone (video_attention.py:80-95): small [n_frames][n] = head sum of att [n_frames][heads][n]
  * times 1 / its frame max, fmax [n_frames] = max of the scaled map, *nonfinite_flag as there.  The clip normalisation is left to

@@ -13,6 +13,7 @@ from .video_attention import VideoAttention  # noqa: F401
 from .checkpoint import latest_file, load_checkpoint, save_checkpoint, save_model  # noqa: F401
 from .pipeline import ClipPipeline  # noqa: F401
 from .video_transform import VideoTransform  # noqa: F401
+from .audio_transform import AudioTransform  # noqa: F401
 from .enhance import Enhancer  # noqa: F401
 
 from . import attn_cache  # noqa: F401

@@ -64,7 +64,7 @@ class Enhancer:
     (default the model's constructed batch, frame_shape[0]); the window buffers are allocated once per call and reused."""
 
     def __init__(self, model, stft, num_frames, num_seq, hops_per_frame, *, video_attention=None, fps=30, sr=16000, attn_diff=False,
-                 target_offset=None, windows_per_launch=None):
+                 target_offset=None, windows_per_launch=None, audio_transform=None):
         if not isinstance(model, AV_Fusion_Model_Frames):
             raise ValueError(f"model must be an AV_Fusion_Model_Frames, got {type(model).__name__}")
         n, s, a = int(num_frames), int(num_seq), int(hops_per_frame)
@@ -86,6 +86,9 @@ class Enhancer:
         wpl = model.frame_shape[0] if windows_per_launch is None else int(windows_per_launch)
         if wpl < 1:
             raise ValueError("windows_per_launch must be positive")
+        if audio_transform is not None and audio_transform.samplerate != sr:
+            raise ValueError(f"audio_transform resamples to {audio_transform.samplerate} Hz, the Enhancer runs at sr={sr}")
+        self.audio_transform = audio_transform
         self.model, self.stft, self.video_attention = model, stft, video_attention
         self.num_frames, self.num_seq, self.hops_per_frame = n, s, a
         self.fps, self.sr, self.attn_diff, self.windows_per_launch = fps, sr, bool(attn_diff), wpl
@@ -105,8 +108,9 @@ class Enhancer:
             e.record()
             self._marks.append((stage, e))
 
-    def _check(self, audio, frames, attn):
-        """Every refusal, on shapes and flags only: nothing here touches the device."""
+    def _check(self, audio, frames, attn, audio_sr=None):
+        """Every refusal, on shapes and flags only: nothing here touches the device.  -> (n_clips, starts, raw): raw = the [1, C, L0]
+        view the audio_transform takes when audio_sr is given, else None."""
         if self.model.training:
             raise ValueError("the model is in training mode: call model.eval() first (train_av_net.py:147); an inference pass must "
                              "not update the BatchNorm running statistics")
@@ -114,24 +118,35 @@ class Enhancer:
             raise ValueError("pass exactly one of frames= (ViT input frames) and attn= (per-frame attention maps)")
         if frames is not None and self.video_attention is None:
             raise ValueError("frames= needs the Enhancer to be built with video_attention=")
-        if not isinstance(audio, torch.Tensor) or audio.dim() != 1 or audio.dtype != torch.float32:
+        raw = None
+        if audio_sr is not None:
+            if self.audio_transform is None:
+                raise ValueError("audio_sr= needs the Enhancer to be built with audio_transform=")
+            if not isinstance(audio, torch.Tensor) or audio.dim() not in (1, 2):
+                raise ValueError(f"audio must be [L0] or [C, L0] with audio_sr=, got {tuple(getattr(audio, 'shape', ()))}")
+            raw, n_samples = self.audio_transform.check(audio, audio_sr)
+        elif not isinstance(audio, torch.Tensor) or audio.dim() != 1 or audio.dtype != torch.float32:
             raise ValueError(f"audio must be a 1-D float32 tensor, got {getattr(audio, 'shape', type(audio))}")
+        else:
+            n_samples = audio.shape[0]
         vid = frames if frames is not None else attn
         ch = 3 if frames is not None else 1
         w = self.model.width
         if not isinstance(vid, torch.Tensor) or vid.dim() != 4 or tuple(vid.shape[1:]) != (ch, w, w) or vid.dtype != torch.float32:
             raise ValueError(f"{'frames' if frames is not None else 'attn'} must be float32 [N, {ch}, {w}, {w}] for this model, got "
                              f"{tuple(getattr(vid, 'shape', ()))} {getattr(vid, 'dtype', '')}")
-        n_clips, starts = self.tiling(audio.shape[0], vid.shape[0])
+        n_clips, starts = self.tiling(n_samples, vid.shape[0])
         if n_clips == 0:
-            raise ValueError(f"the recording ({audio.shape[0]} samples, {vid.shape[0]} frames) is shorter than one clip of "
+            raise ValueError(f"the recording ({n_samples} samples at {self.sr} Hz, {vid.shape[0]} frames) is shorter than one clip of "
                              f"{self.clip_samples} samples and {self.clip_frames} frames")
-        return n_clips, starts
+        return n_clips, starts, raw
 
-    def _prepare(self, audio, frames, attn):
+    def _prepare(self, audio, frames, attn, audio_sr=None):
         """Steps 2-3 for the whole recording: per-frame maps, clip scales, all clip STFTs.  -> dict of device buffers."""
-        n_clips, starts = self._check(audio, frames, attn)
+        n_clips, starts, raw = self._check(audio, frames, attn, audio_sr)
         _lib.require_cuda(audio, frames, attn)
+        if raw is not None:
+            audio = self.audio_transform(raw, audio_sr)[0]          # the recording once: av_dataset.py:203-215, then the tiling at self.sr
         s, a, tc, stft = self.num_seq, self.hops_per_frame, self.clip_frames, self.stft
         dev, st, side = audio.device, stream_ptr(), self.model.width
         used = starts[-1] + tc                          # recording frames the clips use
@@ -177,19 +192,19 @@ class Enhancer:
              side, p["upsample"], int(self.attn_diff), ptr(x_v), st)
         call("maavss_av_stft_windows", ptr(p["y"]), p["n_clips"], a * tc, self.stft.n_bins(), a, s, n, w0, k, ptr(x_a), st)
 
-    def window_inputs(self, audio, frames=None, attn=None):
+    def window_inputs(self, audio, frames=None, attn=None, audio_sr=None):
         """All windows' model inputs at once (inspection; a whole recording's windows take n * S^2 * 4 B each):
         -> (x_a [C*s, 2, a*n, F], x_v [C*s, 1, n, S, S], amax [C]), window c*s + j = window j of clip c."""
-        p = self._prepare(audio, frames, attn)
+        p = self._prepare(audio, frames, attn, audio_sr)
         w = p["n_clips"] * self.num_seq
         x_a = torch.empty(w, 2, self.hops_per_frame * self.num_frames, self.stft.n_bins(), device=audio.device, dtype=torch.float32)
         x_v = torch.empty(w, 1, self.num_frames, self.model.width, self.model.width, device=audio.device, dtype=torch.float32)
         self._gather(p, 0, w, x_a, x_v)
         return x_a, x_v, p["amax"]
 
-    def enhance_stft(self, audio, frames=None, attn=None):
+    def enhance_stft(self, audio, frames=None, attn=None, audio_sr=None):
         """Steps 1-4: -> (stitched [1, 2, a*C*s, F], start)."""
-        p = self._prepare(audio, frames, attn)
+        p = self._prepare(audio, frames, attn, audio_sr)
         n_win, nb, dev = p["n_clips"] * self.num_seq, self.stft.n_bins(), audio.device
         a, n, side, wpl = self.hops_per_frame, self.num_frames, self.model.width, min(self.windows_per_launch, n_win)
         # window buffers once per call, reused by every chunk: memory is bounded by one chunk
@@ -208,10 +223,11 @@ class Enhancer:
                 self._mark("stitch")
         return stitched, self.target_offset * a * self.stft.hop
 
-    def __call__(self, audio, frames=None, attn=None):
-        """audio [L] f32 cuda; frames [N,3,S,S] f32 cuda (the ViT input, needs video_attention) or attn [N,1,S,S] (per-frame maps,
+    def __call__(self, audio, frames=None, attn=None, audio_sr=None):
+        """audio [L] f32 cuda (with audio_sr=, on an Enhancer built with audio_transform=: the raw recording [L0] or [C, L0], f32 or int16,
+        at audio_sr Hz, transformed once to self.sr before the tiling); frames [N,3,S,S] f32 cuda (the ViT input, needs video_attention) or attn [N,1,S,S] (per-frame maps,
         each divided by its own max as VideoAttention._inference / the attention-frame cache give them) -> (wave, start)."""
-        stitched, start = self.enhance_stft(audio, frames, attn)
+        stitched, start = self.enhance_stft(audio, frames, attn, audio_sr)
         wave = self.stft.inverse(stitched)[0]
         self._mark("inverse")
         return wave, start

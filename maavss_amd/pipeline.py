@@ -10,15 +10,23 @@ convolutions) run next to the extractor's full-chip GEMMs instead of in front of
 is reused only after the training step that read it has been enqueued and has signalled its `consumed` event.
 
 With `transform` (a VideoTransform) the pipeline starts one stage earlier, at the decoder's uint8 clips: the frame transform of
-av_dataset.py:315-319 runs on the side stream in front of the extractor, into a per-slot frame buffer.
+av_dataset.py:315-319 runs on the side stream in front of the extractor, into a per-slot frame buffer.  With `audio_transform` (an
+AudioTransform) and `audio_length` (the samples per clip the STFT is to see) the audio side does the same: the demuxer's PCM clips
+at their own rate go through av_dataset.py:203-215 on the side stream in front of the STFT, into a per-slot clip buffer.
 """
 import torch
 
 
 class ClipPipeline:
-    def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None):
+    def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None, audio_transform=None,
+                 audio_length=None):
         self.va, self.stft, self.t = video_attention, stft, clip_frames
         self.transform = transform
+        if audio_transform is None and audio_length is not None:
+            raise ValueError("audio_length needs a ClipPipeline built with audio_transform=")
+        if audio_transform is not None and (isinstance(audio_length, bool) or not isinstance(audio_length, int) or audio_length < 1):
+            raise ValueError(f"audio_transform= needs audio_length=, the samples per clip after the transform, got {audio_length!r}")
+        self.audio_transform, self.audio_length = audio_transform, audio_length
         self.depth = depth
         self.finite_check = finite_check
         self.side = torch.cuda.Stream()
@@ -26,17 +34,36 @@ class ClipPipeline:
         if transform is not None:
             for slot in self.slots:
                 slot["frames"] = None
+        if audio_transform is not None:
+            for slot in self.slots:
+                slot["audio"] = None
         self.head = self.tail = 0            # next slot to submit into / next slot to hand out
 
-    def submit(self, frames, audio, seed, boxes=None):
+    def check_audio(self, audio, audio_sr):
+        """Host-side validation of submit()'s audio arguments (no device work) -> the raw clips as [B, C, L0], None without an
+        audio_transform."""
+        if self.audio_transform is None:
+            if audio_sr is not None:
+                raise ValueError("audio_sr needs a ClipPipeline built with audio_transform=")
+            return None
+        if audio_sr is None:
+            raise ValueError("a ClipPipeline built with audio_transform= needs audio_sr=, the rate of the submitted clips")
+        if not isinstance(audio, torch.Tensor) or audio.dim() not in (2, 3):
+            raise ValueError(f"audio must be [B, C, L0] or [B, L0], got {tuple(getattr(audio, 'shape', ()))}")
+        return self.audio_transform.check(audio, audio_sr, self.audio_length, batched=True)[0]
+
+    def submit(self, frames, audio, seed, boxes=None, audio_sr=None):
         """Enqueue the extraction of one batch: frames [B*T,3,H,W], audio [B,L] (both resident on the device).  The caller's
         stream must already hold the work that produced them (the side stream waits for it).
         With a transform, frames are the uint8 clips [B*T,H0,W0,3] or [B,T,H0,W0,3] and `boxes` the CPU crop boxes [B,4]; by default
-        transform.sample_boxes(B, H0, W0, torch.Generator().manual_seed(seed)), so a pipelined and a serial run see the same crops."""
+        transform.sample_boxes(B, H0, W0, torch.Generator().manual_seed(seed)), so a pipelined and a serial run see the same crops.
+        With an audio_transform, audio is the raw clips [B,C,L0] or [B,L0] (f32 or int16) at `audio_sr` Hz; they must resample to at
+        least audio_length samples and are cropped to that."""
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
         slot = self.slots[self.head % self.depth]
+        raw_audio = self.check_audio(audio, audio_sr)                        # everything is validated before any device work
         if self.transform is not None:
-            raw, _, boxes = self.transform.check(frames, boxes, self.t)      # everything is validated before any device work
+            raw, _, boxes = self.transform.check(frames, boxes, self.t)
             f, h0, w0, _ = raw.shape
             if boxes is None:
                 boxes = self.transform.sample_boxes(f // self.t, h0, w0, torch.Generator().manual_seed(seed))
@@ -62,6 +89,11 @@ class ClipPipeline:
                     slot["frames"] = torch.empty(f, 3, h, w, device=frames.device, dtype=torch.float32)
                 frames = self.transform(raw, boxes=boxes, clip_frames=self.t, out=slot["frames"])
             self.va.attention_frames(frames, clip_frames=self.t, out=slot["attn"], finite_check=self.finite_check)
+            if self.audio_transform is not None:
+                nb = raw_audio.shape[0]
+                if slot["audio"] is None or slot["audio"].shape != (nb, self.audio_length):
+                    slot["audio"] = torch.empty(nb, self.audio_length, device=audio.device, dtype=torch.float32)
+                audio = self.audio_transform(raw_audio, audio_sr, length=self.audio_length, out=slot["audio"])
             slot["x"], slot["y"] = self.stft(audio, seed=seed)    # replaces (frees) the tensors of two batches ago, after the wait above
             slot["ready"].record(self.side)
         self.head += 1
