@@ -375,6 +375,20 @@ int maavss_vit_attn_maps(const float* att, float* out, float* ws, int64_t n_fram
  * upstream store.  The host side (maavss_amd/video_attention.py) raises and names act_dtype="bf16". */
 int maavss_vit_attn_maps_checked(const float* att, float* out, float* ws, int64_t n_frames, int heads, int H, int W,
                                  int clip_frames, int attn_diff, int32_t* nonfinite_flag, void* stream);
+/* Per-head thresholded attention masks, DINO's segmentation read-out (video_attention.py:59-78): for every (frame, head) row a[0..n) of
+ * att [n_frames][heads][n] f32 (what maavss_vit_cls_attn wrote; values >= 0), n = (H / patch) * (W / patch) <= 4096: sort ascending by
+ * value, ties by ascending patch index (torch.sort(stable=True)); v = sorted / sum(a); c = inclusive cumsum(v) in f32; a patch is
+ * kept <=> its c > 1 - threshold; the kept flags are written back at each patch's own position.  The kept set is always a suffix
+ * of the sorted order (everything from the first position with c > 1 - threshold on).  A row whose sum is 0 gives an all-zero mask.
+ * out: values 0 / 1, out_dtype 0 = uint8, 1 = float32 (the reference's .float() at :68); upsample = 0: [n_frames][heads][H / patch]
+ * [W / patch]; upsample = 1: [n_frames][heads][H][W], every patch value repeated patch x patch times (nearest, :70-75), pixels
+ * outside the patch grid (H or W not a multiple of patch) written 0, as in maavss_vit_attn_maps.  threshold in [0, 1].
+ * *nonfinite_flag (device int32, sticky, never cleared here; null = no check) is set to 1 when an input value is inf or NaN, as in
+ * maavss_vit_attn_maps_checked; that row's output is then unspecified (the kernel still terminates and stays in bounds).
+ * One launch, no atomics, deterministic; 16-byte stores when out is 16-byte aligned and the row length (W, or n without upsample)
+ * is a multiple of 16 (uint8) / 4 (float32), element stores otherwise.  Additive in ABI 400. */
+int maavss_vit_attn_masks(const float* att, void* out, int out_dtype, int64_t n_frames, int heads, int H, int W, int patch,
+                          int upsample, float threshold, int32_t* nonfinite_flag, void* stream);
 
 /* ---- EXTENSION (no reference counterpart): AdaptiveAvgPool2d closing the STFT encoder for frame sizes the
  * reference constructor cannot build (224^2, 384^2; SURVEY.md finding 2).  x NHWC [B][H][W][C]; out/dout

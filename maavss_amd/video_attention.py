@@ -12,8 +12,9 @@ num_classes=0), an un-vendored submodule of the reference) is restated from its 
 There is no network in this environment: if the weights file is absent the extractor keeps its seeded random
 initialisation and says so (the reference would try to download).
 
-The dead sort/cumsum/threshold block of the reference (video_attention.py:59-78) never influences the
-returned frames and is not computed.
+The sort/cumsum/threshold block of the reference (video_attention.py:59-78) -- DINO's per-head segmentation masks, which the
+reference computes and then discards -- never influences the returned frames, so `_inference` / `attention_frames` do not
+compute it; `attention_masks` returns it on request (one HIP kernel, maavss_vit_attn_masks), with the constructor's `threshold`.
 """
 import math
 import os
@@ -459,13 +460,7 @@ class VideoAttention:
         "deferred": copy the flag to pinned host memory asynchronously and raise at a later call (once the copy has arrived)
         or at check_finite() -- no host-device synchronisation inside a training step (bench.py); None: no check."""
         _lib.require_cuda(frames)
-        if finite_check not in ("sync", "deferred", None):
-            raise ValueError("finite_check must be 'sync', 'deferred' or None")
-        self.check_finite(wait=False)             # deferred flags of earlier calls that have arrived (never blocks)
-        if finite_check is not None and self._flag is None:
-            self._flag = torch.zeros(1, device=self.device, dtype=torch.int32)
-            self._flag_hosts = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(8)]
-        flag = self._flag if finite_check is not None else None
+        flag = self._finite_flag(finite_check)
         f, _, h, w = frames.shape
         if out is None:
             out = torch.empty(f, 1, h, w, device=frames.device, dtype=torch.float32)
@@ -479,17 +474,98 @@ class VideoAttention:
             ws = torch.empty((e - s) * (hp * wp + 1), device=frames.device, dtype=torch.float32)
             call("maavss_vit_attn_maps_checked", ptr(att), ptr(out[s:e]), ptr(ws), e - s, self.spec.heads, h, w, int(clip_frames),
                  int(bool(attn_diff)), ptr(flag), stream_ptr())
-        if flag is not None:
-            if len(self._flag_pending) >= len(self._flag_hosts):
-                self.check_finite()               # the ring of pinned flag copies is full: wait for the oldest calls
-            used = {id(h) for _, h in self._flag_pending}
-            host = next(h for h in self._flag_hosts if id(h) not in used)
-            host.copy_(flag, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-            self._flag_pending.append((event, host))
-            if finite_check == "sync":
-                self.check_finite()
+        self._finite_flag_read(flag, finite_check)
+        return out
+
+    # ---- the finite guard shared by attention_frames and attention_masks ---------------------------
+    def _finite_flag(self, finite_check):
+        """Before the launches of a guarded call: raise what earlier deferred calls found, -> the sticky device flag (None = no check)."""
+        if finite_check not in ("sync", "deferred", None):
+            raise ValueError("finite_check must be 'sync', 'deferred' or None")
+        self.check_finite(wait=False)             # deferred flags of earlier calls that have arrived (never blocks)
+        if finite_check is not None and self._flag is None:
+            self._flag = torch.zeros(1, device=self.device, dtype=torch.int32)
+            self._flag_hosts = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(8)]
+        return self._flag if finite_check is not None else None
+
+    def _finite_flag_read(self, flag, finite_check):
+        """After the launches: copy the flag to pinned host memory behind them; "sync" waits for it and raises."""
+        if flag is None:
+            return
+        if len(self._flag_pending) >= len(self._flag_hosts):
+            self.check_finite()                   # the ring of pinned flag copies is full: wait for the oldest calls
+        used = {id(h) for _, h in self._flag_pending}
+        host = next(h for h in self._flag_hosts if id(h) not in used)
+        host.copy_(flag, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        self._flag_pending.append((event, host))
+        if finite_check == "sync":
+            self.check_finite()
+
+    def attention_masks(self, frames=None, *, att=None, threshold=None, upsample=True, dtype=torch.uint8, out=None,
+                        finite_check="sync", frame_size=None):
+        """DINO's per-head segmentation masks (video_attention.py:59-78): for every frame and head, the patches that hold the top
+        `threshold` share of the CLS attention mass -- sorted ascending (ties by patch index), normalised, cumulated, kept where the
+        cumulative share exceeds 1 - threshold, written back in patch order -- as 0 / 1 values of `dtype` (torch.uint8, or torch.float32
+        = the reference's .float() at :68).  -> [F, heads, H, W] (each patch repeated 8 x 8, nearest as at :70-75; zero outside the patch
+        grid, as in attention_frames), or [F, heads, H//8, W//8] with upsample=False.
+
+        Exactly one of `frames` ([F,3,H,W] f32 cuda; processed `frames_per_launch` at a time like attention_frames) and `att` (a tensor
+        cls_attention returned, [F, heads, n] f32 cuda: a caller who also wants attention_frames runs the ViT once).  With `att` pass
+        frame_size=(H, W); without it only upsample=False is possible and the masks come back flat, [F, heads, n], like `att`.
+        threshold=None: the constructor's.  finite_check: as in attention_frames (a non-finite CLS attention value raises MaavssError;
+        the masks of such a row are unspecified)."""
+        threshold = self.threshold if threshold is None else threshold
+        if not 0.0 <= float(threshold) <= 1.0:                                                # NaN fails both comparisons
+            raise ValueError(f"threshold={threshold!r}: the kept share of the attention mass must lie in [0, 1]")
+        if (frames is None) == (att is None):
+            raise ValueError("attention_masks takes exactly one of `frames` and `att`")
+        if dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"dtype={dtype!r}: masks are written as torch.uint8 or torch.float32")
+        if finite_check not in ("sync", "deferred", None):
+            raise ValueError("finite_check must be 'sync', 'deferred' or None")
+        _lib.require_cuda(frames, att, out)
+        if frames is not None:
+            if frames.dim() != 4 or frames.shape[1] != 3 or frames.dtype != torch.float32:
+                raise ValueError(f"frames must be [F, 3, H, W] float32, got {tuple(frames.shape)} {frames.dtype}")
+            if frame_size is not None and tuple(frame_size) != tuple(frames.shape[2:]):
+                raise ValueError(f"frame_size={tuple(frame_size)} contradicts frames of {tuple(frames.shape[2:])}")
+            f, heads, (h, w) = frames.shape[0], self.spec.heads, frames.shape[2:]
+        else:
+            if att.dim() != 3 or att.dtype != torch.float32:
+                raise ValueError(f"att must be the [F, heads, n] float32 tensor of cls_attention, got {tuple(att.shape)} {att.dtype}")
+            att = att.contiguous()
+            f, heads, n = att.shape
+            if frame_size is None:
+                if upsample:
+                    raise ValueError("attention_masks(att=...) needs frame_size=(H, W) to upsample (or upsample=False)")
+                h, w = PATCH, PATCH * n               # one row of n patches: the flat layout of `att`
+            else:
+                h, w = (int(v) for v in frame_size)
+                if (h // PATCH) * (w // PATCH) != n:
+                    raise ValueError(f"frame_size={(h, w)} has {(h // PATCH) * (w // PATCH)} patches, att has {n}")
+        if upsample:
+            shape = (f, heads, h, w)
+        else:
+            shape = (f, heads, n) if frames is None and frame_size is None else (f, heads, h // PATCH, w // PATCH)
+        if out is None:
+            out = torch.empty(shape, device=self.device if frames is None else frames.device, dtype=dtype)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape}, got {tuple(out.shape)} {out.dtype}")
+        if f == 0:
+            return out
+        flag = self._finite_flag(finite_check)
+        code, up = (1 if dtype == torch.float32 else 0), int(bool(upsample))
+        if frames is None:
+            call("maavss_vit_attn_masks", ptr(att), ptr(out), code, f, heads, h, w, PATCH, up, float(threshold), ptr(flag), stream_ptr())
+        else:
+            for s in range(0, f, self.frames_per_launch):
+                e = min(f, s + self.frames_per_launch)
+                a = self.cls_attention(frames[s:e])
+                call("maavss_vit_attn_masks", ptr(a), ptr(out[s:e]), code, e - s, heads, h, w, PATCH, up, float(threshold), ptr(flag),
+                     stream_ptr())
+        self._finite_flag_read(flag, finite_check)
         return out
 
     def _inference(self, frames):
