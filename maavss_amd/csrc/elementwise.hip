@@ -168,7 +168,8 @@ extern "C" int maavss_adaptive_pool_bwd(const float* dout, float* dx, int B, int
 __global__ __launch_bounds__(256) void bias_act_kernel(float* __restrict__ z, const float* __restrict__ bias, int64_t total, int n,
                                                        int act, float slope) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    float v = z[i] + (bias ? bias[i % n] : 0.f);
+    float v = z[i];
+    if (bias) v += bias[i % n];      // not `+ 0.f` without a bias: that would turn -0.0 into +0.0
     if (act == 3) v = v > 0.f ? v : v * slope;
     z[i] = v;
   }

@@ -44,18 +44,26 @@ def stft_ref(audio, fft_len, hop, normalized=True, trim_stft_end=False):
     return spec.permute(*range(spec.dim() - 3), -1, -2, -3).contiguous()
 
 
-def stft_direct_f64(audio, fft_len, hop, normalized=True):
-    """Independent restatement: reflect pad, frame, window, DFT in float64."""
+def stft_direct_f64(audio, fft_len, hop, normalized=True, n_frames=None, n_bins=None):
+    """Independent restatement: reflect, frame, window, DFT in float64 -> [..., 2, n_frames, n_bins].
+    `n_frames` defaults to L // hop (the 1 + L // hop frames of torch.stft minus the dropped last one) and `n_bins` to
+    fft_len / 2 + 1.  Sample j of the centred signal is read at |j| on the left and at 2 (L - 1) - j on the right, which
+    is the reflect padding for every frame torch.stft produces and carries on past it for a larger `n_frames` (the
+    C-ABI admits frames up to the one whose last sample reflects onto index 0).  The index form is the one a kernel would
+    use too; what keeps this an independent reference is the CPU check against torch.stft, which pads by its own code, at
+    the odd shapes and against an explicitly mirrored signal for the frames past torch's own."""
     a = audio.double()
-    half = fft_len // 2
-    left = a[..., 1:half + 1].flip(-1)
-    right = a[..., -half - 1:-1].flip(-1)
-    p = torch.cat([left, a, right], -1)
-    n_frames = 1 + a.shape[-1] // hop
-    idx = torch.arange(n_frames)[:, None] * hop + torch.arange(fft_len)[None, :]
+    length = a.shape[-1]
+    n_frames = length // hop if n_frames is None else n_frames
+    n_bins = fft_len // 2 + 1 if n_bins is None else n_bins
+    j = torch.arange(n_frames)[:, None] * hop + torch.arange(fft_len)[None, :] - fft_len // 2
+    j = j.abs()
+    j = torch.where(j >= length, 2 * (length - 1) - j, j)
+    if int(j.min()) < 0 or int(j.max()) >= length:
+        raise ValueError("frames run past the reflected signal")
     win = hamming_periodic(fft_len, torch.float64)
-    fr = p[..., idx] * win                          # [..., frames, n]
-    k = torch.arange(fft_len // 2 + 1, dtype=torch.float64)[:, None]
+    fr = a[..., j] * win                            # [..., frames, n]
+    k = torch.arange(n_bins, dtype=torch.float64)[:, None]
     n = torch.arange(fft_len, dtype=torch.float64)[None, :]
     ang = -2 * math.pi * k * n / fft_len
     re = fr @ torch.cos(ang).T
@@ -63,7 +71,7 @@ def stft_direct_f64(audio, fft_len, hop, normalized=True):
     out = torch.stack([re, im], -3)                 # [..., 2, frames, F]
     if normalized:
         out = out / win.pow(2).sum().sqrt()
-    return out[..., :-1, :]
+    return out
 
 
 def gen_stft_example_ref(audio, fft_len, hop, sigma, noise, normalized=True, normalize_output=False):
@@ -87,12 +95,14 @@ def synthetic_audio(batch, length, seed, sr=16000):
     return a.clamp(-1, 1)
 
 
-def istft_ref(stft, fft_len, hop, normalized=True, trim_stft_end=False):
+def istft_ref(stft, fft_len, hop, normalized=True, trim_stft_end=False, dtype=torch.float32):
     """AV_Dataset.istft (av_dataset.py:181-201), batched: stft [B,2,T_a,F] -> audio [B, hop*(T_a-1)].
     The reference hands torch.istft the real view [F,T,2] (accepted by the torch of its day); the same function takes
-    the complex tensor today -- same arithmetic."""
+    the complex tensor today -- same arithmetic.  dtype=torch.float64 evaluates the same call on complex128 with a
+    float64 window."""
+    stft = stft.to(dtype)
     if trim_stft_end:
         stft = torch.nn.functional.pad(stft, (0, 1))
     spec = torch.complex(stft[:, 0], stft[:, 1]).transpose(1, 2).contiguous()          # [B, F, T]
-    return torch.istft(spec, n_fft=fft_len, hop_length=hop, win_length=fft_len, window=hamming_periodic(fft_len),
+    return torch.istft(spec, n_fft=fft_len, hop_length=hop, win_length=fft_len, window=hamming_periodic(fft_len, dtype),
                        normalized=normalized, onesided=True)
