@@ -194,8 +194,9 @@ class AV_Fusion_Model_Frames(nn.Module):
         # the bf16 backward gates the 16-bit backward kernels at model level; the 16-bit forward's MaxPool / LeakyReLU re-routing is
         # then out of the picture).  `precise=` sets both; product code never sets them apart.
         self.precise_fwd = self.precise_bwd = self.precise
-        # 16-bit path: the first layer's conv output is recomputed instead of stored (MAAVSS_C1_RECOMPUTE=0: the storing kernels, for A/B)
-        self.c1_recompute = os.environ.get("MAAVSS_C1_RECOMPUTE", "1") != "0"
+        # 16-bit path: the first layer's conv output is recomputed instead of stored (False: the storing kernels, which also serve the
+        # eval-mode and `precise` forwards)
+        self.c1_recompute = True
         self._bn_sync = None
         if self.frame_channels != 1:
             raise ValueError("the visual encoder takes single-channel attention frames (avse_model_final.py:34)")
@@ -708,13 +709,9 @@ class AV_Fusion_Model_Frames(nn.Module):
                                      reduce_fn=bn_reduce, dy_bf16=not self.precise_bwd)
             if need.get(wname, False):
                 buf, beta = gbuf(wname)
-                if i == 0:
-                    ops.conv3d_c1_wgrad(s["x"], dy, dw=buf, beta=beta)
-                else:
-                    xw = s["x_bf16"] if s.get("x_bf16") is not None and dy.dtype == torch.bfloat16 else s["x"]
-                    ops.conv3d_wgrad(xw, dy, pad, pr_conv, dw=buf, beta=beta)
+                xw = s["x_bf16"] if s.get("x_bf16") is not None and dy.dtype == torch.bfloat16 else s["x"]
+                ops.conv3d_wgrad(xw, dy, pad, pr_conv, dw=buf, beta=beta)
                 out_grads[wname] = buf
-            if i > 0:
-                wtd = ops.conv3d_prep(conv.weight.detach(), 1, pr_conv)
-                dcur, _ = ops.conv3d_igemm(dy, wtd, conv.in_channels, 4 - pad, pr_conv)
+            wtd = ops.conv3d_prep(conv.weight.detach(), 1, pr_conv)
+            dcur, _ = ops.conv3d_igemm(dy, wtd, conv.in_channels, 4 - pad, pr_conv)
         return out_grads

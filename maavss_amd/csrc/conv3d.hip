@@ -16,7 +16,6 @@
 //                    partial; a second kernel sums the chunks (deterministic, no atomics).
 #include <type_traits>
 #include <utility>
-#include <cstdlib>
 #include "mma.h"
 
 // --------------------------------------------------------------------------------------------
@@ -94,46 +93,27 @@ static inline int xcd_grid(int64_t total) { return (int)(((total + 7) / 8) * 8);
 // Tile HEIGHT of the 16-wide output tiles (round 4): 14 rows when that covers the plane with as many tiles as 16 would (56 -> 4 x 14, 28 -> 2 x 14:
 // the layers at 56^2 and 28^2 spent 12.5 % of their MFMAs on rows below the image), else 16.  A tile's rows are dealt to the four waves as
 // 4 + 4 + 3 + 3 (first row 0, 4, 8, 11); the number of tiles -- and of BatchNorm partial rows -- is the same for both heights by construction.
-int maavss_conv_tile_h(int Ho) {      // (also conv3d_wgrad_wide.hip)
-  static const bool only16 = getenv("MAAVSS_TILE_H16") != nullptr;      // A/B switch
-  return !only16 && cdiv(Ho, 14) == cdiv(Ho, 16) ? 14 : 16;
-}
-static inline int conv_tile_h(int Ho) { return maavss_conv_tile_h(Ho); }
+int maavss_conv_tile_h(int Ho) { return cdiv(Ho, 14) == cdiv(Ho, 16) ? 14 : 16; }      // (also conv3d_wgrad_wide.hip)
 __device__ __forceinline__ int tile_row0(int wv, int th) { return th == 14 ? 4 * wv - (wv > 2 ? wv - 2 : 0) : 4 * wv; }
 __device__ __forceinline__ int tile_nrows(int wv, int th) { return th == 14 && wv >= 2 ? 3 : 4; }
 
-// IN16: x is already stored in the MFMA operand format (IEEE half for the forward pass, bf16 for the input-gradient pass:
-// the producers bn_pool_act_fwd / bn_pool_act_bwd round once instead of every consumer) -- the halo is then a plain copy of
-// half the bytes: by LDS-DMA for C_in = 16 / 32 (no staging registers: these variants are VGPR-limited and ran a
-// load -> convert -> store loop with ONE load in flight per thread, a third of their time), by the register prefetch for 64.
-template <int PRECISE, int CIN, int COUT, bool IN16 = false>
-__global__ __launch_bounds__(256) void conv3d_igemm_kernel(const void* __restrict__ x_,
-                                                           const typename Mma<PRECISE>::elem* __restrict__ wt,
+// The exact-f32 implicit GEMM (precise = MODE_F32; the 16-bit modes are conv3d_igemm16_kernel below): x, the weights and the LDS images
+// are f32, a 32-deep K step is eight v_mfma_f32_16x16x4_f32 (mma.h).  Per kd the 20x20xC_in halo is staged once; the weight tiles of
+// 64 k go global -> registers -> LDS one chunk ahead of their use, into a double buffer.
+template <int CIN, int COUT>
+__global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float* __restrict__ x, const float* __restrict__ wt,
                                                            float* __restrict__ y, float* __restrict__ stat_partials,
                                                            int n_bt, int T, int H, int W, int Ho, int Wo, int pad, int KP, int th) {
-  using M = Mma<PRECISE>;
-  static_assert(!IN16 || PRECISE != MODE_F32, "16-bit input needs a 16-bit MFMA mode");
-  const float* x = reinterpret_cast<const float*>(x_);
-  const unsigned short* x16 = reinterpret_cast<const unsigned short*>(x_);
-  using E = typename M::elem;
-  constexpr int ES = sizeof(E), EPC = 16 / ES;       // elements per 16-byte chunk
-  // 16-bit input with 64 channels: the halo is staged in two halves of 32 channels (K order kd, half, tap, channel): 25.6 KB by LDS-DMA
-  // like the 32-channel variants instead of 51 KB through a 100-register prefetch -- three to four workgroups per CU instead of two
-  constexpr bool HSPLIT = PRECISE != MODE_F32 && CIN == 64;      // (also for f32 input: the two input forms stay bit-identical)
-  constexpr int CH = HSPLIT ? 32 : CIN;               // channels per halo stage
-  constexpr int NH = CIN / CH;                        // halo stages per kd plane
-  constexpr int RBH = CH * ES, NCH = RBH / 16;        // halo: bytes / chunks per position
-  constexpr int RBW = 64 * ES, NCW = RBW / 16;        // weight tile: bytes / chunks per row (64 k)
+  using M = Mma<MODE_F32>;
+  constexpr int EPC = 4;                              // f32 elements per 16-byte chunk
+  constexpr int RBH = CIN * 4, NCH = RBH / 16;        // halo: bytes / chunks per position
+  constexpr int RBW = 64 * 4, NCW = RBW / 16;         // weight tile: bytes / chunks per row (64 k)
   constexpr int NT = COUT / 16;
-  constexpr int NCHUNK = (25 * CH + 63) / 64;
+  constexpr int NCHUNK = (25 * CIN + 63) / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  E* halo = reinterpret_cast<E*>(smem);                         // [20*20][CH] swizzled
-  // 16-bit modes (round 4): the weight tiles go global -> LDS by DMA into a RING OF THREE, two chunks ahead of their use, instead of through
-  // registers one chunk ahead: at 56^2 / 28^2 these launches are bound by the 307 / 614 KB of weights every tile pulls through LDS, not by MFMAs
-  constexpr bool WDMA = PRECISE != MODE_F32;
-  constexpr int WSLOTS = WDMA ? 3 : 2;
-  E* wl = halo + 400 * CH;                                      // [WSLOTS][COUT][64] swizzled
-  float* red = reinterpret_cast<float*>(wl + WSLOTS * COUT * 64);    // [4][2][COUT] stats scratch
+  float* halo = reinterpret_cast<float*>(smem);                 // [20*20][CIN] swizzled
+  float* wl = halo + 400 * CIN;                                 // [2][COUT][64] swizzled
+  float* red = wl + 2 * COUT * 64;                              // [4][2][COUT] stats scratch
 
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, l16 = lane & 15;
@@ -152,15 +132,14 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const void* __restric
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- halo staging.  C_in = 64: the 25 float4 of a thread's share of the NEXT frame's halo are requested before this
-  // frame's MFMAs and converted / written to LDS after them (register prefetch).  With a plain load -> convert -> store
+  // frame's MFMAs and written to LDS after them (register prefetch).  With a plain load -> store
   // loop one load is in flight per thread: 25 dependent round trips per frame, and these variants run only two
   // workgroups per CU (60 - 70 KB of LDS each), too few to cover that; the same LDS limit leaves 256 VGPRs per lane,
   // so the 100 staging registers are free.  (Scratch build without the halo loads: igemm 4.3 -> 2.9 ms per step.)
   // The smaller C_in variants run 3 - 5 workgroups per CU and keep the plain loop (batched loads cost them occupancy).
-  constexpr int VE = IN16 ? 8 : 4;                      // elements per 16-byte global vector
-  constexpr int HV = 400 * (CH / VE), NV = (HV + 255) / 256;
-  constexpr bool PREFETCH = CIN >= 64 && !HSPLIT;
-  float4 hv[PREFETCH ? NV : 1];                         // IN16: the same 16 bytes hold 8 operand elements
+  constexpr int HV = 400 * (CIN / 4), NV = (HV + 255) / 256;
+  constexpr bool PREFETCH = CIN >= 64;
+  float4 hv[PREFETCH ? NV : 1];
   auto fetch = [&](int kd) __attribute__((always_inline)) {
     const int64_t plane = (int64_t)(bt + kd - 1) * H * W * CIN;
     int tv = tid;
@@ -168,14 +147,13 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const void* __restric
 #pragma unroll
     for (int j = 0; j < (PREFETCH ? NV : 1); ++j) {
       const int i = tv + j * 256;
-      const int pos = i / (CIN / VE), cv = (i % (CIN / VE)) * VE;
+      const int pos = i / (CIN / 4), cv = (i % (CIN / 4)) * 4;
       const int r = pos / 20, c = pos % 20;
       const int iy = y0 + r - pad, ix = x0 + c - pad;
       hv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (i < HV && iy >= 0 && iy < H && ix >= 0 && ix < W) {
         const int64_t e = plane + ((int64_t)iy * W + ix) * CIN + cv;
-        if constexpr (IN16) hv[j] = *reinterpret_cast<const float4*>(x16 + e);
-        else hv[j] = *reinterpret_cast<const float4*>(x + e);
+        hv[j] = *reinterpret_cast<const float4*>(x + e);
       }
     }
   };
@@ -186,141 +164,77 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const void* __restric
     for (int j = 0; j < (PREFETCH ? NV : 1); ++j) {
       const int i = tv + j * 256;
       if (i < HV) {
-        const int pos = i / (CIN / VE), cv = (i % (CIN / VE)) * VE, c = pos % 20;
-        E* d = halo + (pos * NCH + swz_halo<RBH, ES>(c, cv / EPC)) * EPC + (cv % EPC);
-        if constexpr (IN16) {
-          *reinterpret_cast<float4*>(d) = hv[j];
-        } else {
-          d[0] = M::cvt(hv[j].x); d[1] = M::cvt(hv[j].y); d[2] = M::cvt(hv[j].z); d[3] = M::cvt(hv[j].w);
-        }
+        const int pos = i / (CIN / 4), cv = (i % (CIN / 4)) * 4, c = pos % 20;
+        float* d = halo + (pos * NCH + swz<RBH>(c, cv / EPC)) * EPC;
+        d[0] = hv[j].x; d[1] = hv[j].y; d[2] = hv[j].z; d[3] = hv[j].w;
       }
     }
   };
   const int kd_lo = t == 0 ? 1 : 0, kd_hi = t == T - 1 ? 1 : 2;   // frames t + kd - 1 inside the clip (block-uniform)
   if constexpr (PREFETCH) fetch(kd_lo);
-  for (int kd = kd_lo; kd <= kd_hi; ++kd)
-  for (int hh = 0; hh < NH; ++hh) {
+  for (int kd = kd_lo; kd <= kd_hi; ++kd) {
     __syncthreads();
-    // ---- stage the 20x20xCH halo of frame t + kd - 1 (zero-filled outside the image)
+    // ---- stage the 20x20xC_in halo of frame t + kd - 1 (zero-filled outside the image)
     if constexpr (PREFETCH) {
       stash();
-    } else if constexpr (IN16) {
-      // LDS-DMA: 16 B per lane straight into the halo image.  The DMA writes lane-linearly (slot i = position i / NCH, physical
-      // chunk i % NCH), so the swizzle is applied on the SOURCE side (XOR: its own inverse).  Positions outside the image read
-      // the zero padding at the end of weight row 0 (k >= 25 C_in: maavss_conv3d_kp leaves at least 64 bytes) -- no predication, the
-      // wave stays whole, the destination base stays lane 0's.
-      const unsigned short* xp = x16 + (int64_t)(bt + kd - 1) * H * W * CIN + hh * CH;
-      const unsigned short* zeros = reinterpret_cast<const unsigned short*>(wt) + 25 * CIN;
-      const int hv_rt = hpos * NCH;               // (th + 4) halo rows
-      for (int i0 = 0; i0 < hv_rt; i0 += 256) {
-        const int i = i0 + tid;
-        if (i < hv_rt) {
-          const int pos = i / NCH, pc = i % NCH;
-          const int r = pos / 20, c = pos % 20;
-          const int iy = y0 + r - pad, ix = x0 + c - pad;
-          const unsigned short* src = zeros;
-          if (iy >= 0 && iy < H && ix >= 0 && ix < W) src = xp + ((int64_t)iy * W + ix) * CIN + swz_halo<RBH, ES>(c, pc) * EPC;
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                           (__attribute__((address_space(3))) void*)(halo + (int64_t)i * EPC), 16, 0, 0);
-        }
-      }
     } else {
-      const float* xp = x + (int64_t)(bt + kd - 1) * H * W * CIN + hh * CH;
-      for (int i = tid; i < hpos * (CH / 4); i += 256) {
-        const int pos = i / (CH / 4), c4 = (i % (CH / 4)) * 4;
+      const float* xp = x + (int64_t)(bt + kd - 1) * H * W * CIN;
+      for (int i = tid; i < hpos * (CIN / 4); i += 256) {
+        const int pos = i / (CIN / 4), c4 = (i % (CIN / 4)) * 4;
         const int r = pos / 20, c = pos % 20;
         const int iy = y0 + r - pad, ix = x0 + c - pad;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = *reinterpret_cast<const float4*>(xp + ((int64_t)iy * W + ix) * CIN + c4);
-        E* d = halo + (pos * NCH + swz_halo<RBH, ES>(c, c4 / EPC)) * EPC + (c4 % EPC);
-        d[0] = M::cvt(v.x); d[1] = M::cvt(v.y); d[2] = M::cvt(v.z); d[3] = M::cvt(v.w);
+        float* d = halo + (pos * NCH + swz<RBH>(c, c4 / EPC)) * EPC;
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
       }
     }
-    // ---- weight chunks of this (kd, half).  Source of the 16-byte piece c of row n of chunk q: k = 64 q + 8 c, or with the halo in
-    // halves k = (2 q + c / 4) * 64 + 32 half + 8 (c % 4) -- two taps x 32 channels; the phantom tap 25 of the last chunk is the zero tail
-    const E* wk = wt + (int64_t)kd * COUT * KP;
-    auto wsrc = [&](int i, int q) __attribute__((always_inline)) {
-      const int n = i / NCW, c = i % NCW;
-      if constexpr (HSPLIT) return wk + (int64_t)n * KP + (2 * q + c / 4) * 64 + hh * 32 + (c % 4) * EPC;
-      else return wk + (int64_t)n * KP + q * 64 + c * EPC;
-    };
+    // ---- weight chunks of this kd: the 16-byte piece c of row n of chunk q starts at k = 64 q + 4 c
+    const float* wk = wt + (int64_t)kd * COUT * KP;
+    auto wsrc = [&](int i, int q) __attribute__((always_inline)) { return wk + (int64_t)(i / NCW) * KP + q * 64 + (i % NCW) * EPC; };
     constexpr int WV = (COUT * NCW + 255) / 256;
-    // DMA of chunk q into ring slot `slot`: lane-linear destination (piece i = row i / 8, physical chunk i % 8), swizzle on the source side
-    auto wdma = [&](int q, int slot) __attribute__((always_inline)) {
-#pragma unroll
-      for (int v = 0; v < WV; ++v) {
-        const int i = v * 256 + tid;
-        if (WV * 256 == COUT * NCW || i < COUT * NCW) {
-          const int n = i / NCW, pc = i % NCW;
-          const E* src = wsrc(n * NCW + swz<RBW>(n, pc), q);
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                           (__attribute__((address_space(3))) void*)(wl + slot * COUT * 64 + (int64_t)i * EPC), 16, 0, 0);
-        }
-      }
-    };
-    if constexpr (WDMA) {
-      wdma(0, 0);
-      if (NCHUNK > 1) wdma(1, 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // halo (DMA) and the first two weight tiles have landed
-      __syncthreads();
-    } else {
-      for (int i = tid; i < COUT * NCW; i += 256) {
-        const int n = i / NCW, c = i % NCW;
-        *reinterpret_cast<uint4*>(wl + (n * NCW + swz<RBW>(n, c)) * EPC) = *reinterpret_cast<const uint4*>(wsrc(i, 0));
-      }
-      if constexpr (IN16 && !PREFETCH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the halo DMA has landed
-      __syncthreads();
+    for (int i = tid; i < COUT * NCW; i += 256) {
+      const int n = i / NCW, c = i % NCW;
+      *reinterpret_cast<uint4*>(wl + (n * NCW + swz<RBW>(n, c)) * EPC) = *reinterpret_cast<const uint4*>(wsrc(i, 0));
     }
+    __syncthreads();
     if constexpr (PREFETCH) {
       if (kd < kd_hi) fetch(kd + 1);
     }
-    int slot = 0;
     for (int ch = 0; ch < NCHUNK; ++ch) {
-      uint4 wreg[WDMA ? 1 : WV];
-      if constexpr (WDMA) {
-        // slot of chunk ch + 2 = slot of chunk ch - 1: every wave is past the barrier that ended it
-        if (ch + 2 < NCHUNK) wdma(ch + 2, slot == 0 ? 2 : slot - 1);
-      } else {
-        // unconditional (clamped) loads keep wreg in registers: a conditionally written array lands in scratch
-        const int chn = ch + 1 < NCHUNK ? ch + 1 : ch;
+      // the next chunk's tile, global -> registers; unconditional (clamped) loads keep wreg in registers: a conditionally written
+      // array lands in scratch
+      uint4 wreg[WV];
+      const int chn = ch + 1 < NCHUNK ? ch + 1 : ch;
 #pragma unroll
-        for (int v = 0; v < WV; ++v) {
-          int i = v * 256 + tid;
-          i = i < COUT * NCW ? i : 0;
-          wreg[v] = *reinterpret_cast<const uint4*>(wsrc(i, chn));
-        }
+      for (int v = 0; v < WV; ++v) {
+        int i = v * 256 + tid;
+        i = i < COUT * NCW ? i : 0;
+        wreg[v] = *reinterpret_cast<const uint4*>(wsrc(i, chn));
       }
-      const E* wb = wl + (WDMA ? slot : (ch & 1)) * COUT * 64;
+      const float* wb = wl + (ch & 1) * COUT * 64;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const int kk = ch * 64 + s * 32 + 8 * g;
-        int tap = kk / CH;
-        const int ci = kk % CH;
+        int tap = kk / CIN;
+        const int ci = kk % CIN;
         tap = tap > 24 ? 24 : tap;  // padded tail: weights are zero there
         const int kh = tap / 5, kw = tap % 5;
-        typename M::frag fa[4], fb[NT];
+        M::frag fa[4], fb[NT];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = row0 + i + kh, c = l16 + kw;
-          const E* base = halo + (r * 20 + c) * NCH * EPC;
-          if constexpr (PRECISE == MODE_F32) {
-            fa[i].lo = *reinterpret_cast<const f32x4*>(base + swz_halo<RBH, ES>(c, ci / EPC) * EPC);
-            fa[i].hi = *reinterpret_cast<const f32x4*>(base + swz_halo<RBH, ES>(c, ci / EPC + 1) * EPC);
-          } else {
-            fa[i] = M::load(base + swz_halo<RBH, ES>(c, ci / EPC) * EPC);
-          }
+          const float* base = halo + (r * 20 + c) * NCH * EPC;
+          fa[i].lo = *reinterpret_cast<const f32x4*>(base + swz<RBH>(c, ci / EPC) * EPC);
+          fa[i].hi = *reinterpret_cast<const f32x4*>(base + swz<RBH>(c, ci / EPC + 1) * EPC);
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
           const int n = j * 16 + l16;
-          const E* base = wb + n * 64;
+          const float* base = wb + n * 64;
           const int c0 = (s * 32 + 8 * g) / EPC;
-          if constexpr (PRECISE == MODE_F32) {
-            fb[j].lo = *reinterpret_cast<const f32x4*>(base + swz<RBW>(n, c0) * EPC);
-            fb[j].hi = *reinterpret_cast<const f32x4*>(base + swz<RBW>(n, c0 + 1) * EPC);
-          } else {
-            fb[j] = M::load(base + swz<RBW>(n, c0) * EPC);
-          }
+          fb[j].lo = *reinterpret_cast<const f32x4*>(base + swz<RBW>(n, c0) * EPC);
+          fb[j].hi = *reinterpret_cast<const f32x4*>(base + swz<RBW>(n, c0 + 1) * EPC);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -329,31 +243,18 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const void* __restric
             for (int j = 0; j < NT; ++j) M::mma(acc[i][j], fa[i], fb[j]);
           }
       }
-      if constexpr (WDMA) {
-        // chunk ch + 1 must have landed (this wave's pieces; the barrier collects the others'), chunk ch + 2 may stay in flight
-        if (ch + 2 < NCHUNK) {
-          if constexpr (WV == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        slot = slot == 2 ? 0 : slot + 1;
-      } else {
-        if (ch + 1 < NCHUNK) {
-          E* wn = wl + ((ch + 1) & 1) * COUT * 64;
+      if (ch + 1 < NCHUNK) {
+        float* wn = wl + ((ch + 1) & 1) * COUT * 64;
 #pragma unroll
-          for (int v = 0; v < WV; ++v) {
-            const int i = v * 256 + tid;
-            if (i < COUT * NCW) {
-              const int n = i / NCW, c = i % NCW;
-              *reinterpret_cast<uint4*>(wn + (n * NCW + swz<RBW>(n, c)) * EPC) = wreg[v];
-            }
+        for (int v = 0; v < WV; ++v) {
+          const int i = v * 256 + tid;
+          if (i < COUT * NCW) {
+            const int n = i / NCW, c = i % NCW;
+            *reinterpret_cast<uint4*>(wn + (n * NCW + swz<RBW>(n, c)) * EPC) = wreg[v];
           }
         }
-        __syncthreads();
       }
+      __syncthreads();
     }
   }
   // ---- epilogue: store + optional per-block BatchNorm partial sums (sum, sum of squares per channel)
@@ -396,16 +297,16 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const void* __restric
   }
 }
 
-template <int PRECISE, int CIN, int COUT, bool IN16 = false>
+template <int CIN, int COUT>
 static int launch_igemm(const void* x, const void* wt, float* y, float* stats, int B, int T, int H, int W, int Ho,
                         int Wo, int pad, int KP, hipStream_t st) {
-  using E = typename Mma<PRECISE>::elem;
-  const int th = conv_tile_h(Ho);
-  const size_t smem = (400 * (PRECISE != MODE_F32 && CIN == 64 ? 32 : CIN) + (PRECISE != MODE_F32 ? 3 : 2) * COUT * 64) * sizeof(E) + 8 * COUT * sizeof(float);
-  auto kern = conv3d_igemm_kernel<PRECISE, CIN, COUT, IN16>;
+  const int th = maavss_conv_tile_h(Ho);
+  const size_t smem = (400 * CIN + 2 * COUT * 64 + 8 * COUT) * sizeof(float);      // halo, two weight tiles, stats scratch
+  auto kern = conv3d_igemm_kernel<CIN, COUT>;
   if (smem > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int64_t tiles = (int64_t)cdiv(Wo, 16) * cdiv(Ho, th) * B * T;
-  hipLaunchKernelGGL(kern, dim3(xcd_grid(tiles)), dim3(256), smem, st, x, reinterpret_cast<const E*>(wt), y, stats, B * T, T, H, W, Ho, Wo, pad, KP, th);
+  hipLaunchKernelGGL(kern, dim3(xcd_grid(tiles)), dim3(256), smem, st, reinterpret_cast<const float*>(x), reinterpret_cast<const float*>(wt), y, stats,
+                     B * T, T, H, W, Ho, Wo, pad, KP, th);
   return 0;
 }
 
@@ -647,7 +548,7 @@ static int launch_igemm16(const void* x, const void* wt, float* y, float* stats,
     const size_t smem = 400 * (CIN == 64 ? 32 : CIN) * 2 + 4 * COUT * 128 + 8 * COUT * sizeof(float);
     auto kern = conv3d_igemm16_kernel<PRECISE, CIN, COUT, IN16>;
     if (smem > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    const int th = conv_tile_h(Ho);
+    const int th = maavss_conv_tile_h(Ho);
     const int64_t tiles = (int64_t)cdiv(Wo, 16) * cdiv(Ho, th) * B * T;
     hipLaunchKernelGGL(kern, dim3(xcd_grid(tiles)), dim3(256), smem, st, x, reinterpret_cast<const E*>(wt), y, stats, B * T, T, H, W, Ho, Wo, pad, KP, th);
     return 0;
@@ -683,16 +584,10 @@ extern "C" int maavss_conv3d_igemm(const void* x, const void* wt, float* y, floa
   MAAVSS_CHECK_ARG((int64_t)cdiv(Wo, 16) * cdiv(Ho, 16) * B * T < (1LL << 31) - 8, "conv3d_igemm: too many output tiles");
   const int KP = maavss_conv3d_kp(c_in);
   hipStream_t st = (hipStream_t)stream;
-  // 16-bit modes: the pipelined kernel (conv3d_igemm16_kernel); MAAVSS_IGEMM_OLD=1 = the round-1..3 loop, kept as the measured baseline
-  // (profiles/r4_igemm_bench.txt) and as the exact-f32 path
-  static const bool old16 = getenv("MAAVSS_IGEMM_OLD") != nullptr;
+  // MODE_F32: the exact-f32 kernel; the 16-bit modes: the pipelined kernel (conv3d_igemm16_kernel)
 #define CASE(CI, CO)                                                                                          \
   if (c_in == CI && c_out == CO) {                                                                            \
-    if (precise == MODE_F32) launch_igemm<MODE_F32, CI, CO>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st);      \
-    else if (old16 && precise == MODE_F16 && x16) launch_igemm<MODE_F16, CI, CO, true>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st); \
-    else if (old16 && precise == MODE_F16) launch_igemm<MODE_F16, CI, CO>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st); \
-    else if (old16 && x16) launch_igemm<MODE_BF16, CI, CO, true>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st);         \
-    else if (old16) launch_igemm<MODE_BF16, CI, CO>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st);                        \
+    if (precise == MODE_F32) launch_igemm<CI, CO>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st);  \
     else if (precise == MODE_F16 && x16) launch_igemm16<MODE_F16, CI, CO, true>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st); \
     else if (precise == MODE_F16) launch_igemm16<MODE_F16, CI, CO, false>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st); \
     else if (x16) launch_igemm16<MODE_BF16, CI, CO, true>(x, wt, y, stat_partials, B, T, H, W, Ho, Wo, pad, KP, st);         \

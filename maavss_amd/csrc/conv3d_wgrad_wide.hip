@@ -322,7 +322,7 @@ static void launch_wide(const float* x, const void* dy, float* ws, int BT, int T
                                    : (size_t)(KDN * (CI / 16) * (400 * 16 + 32) + (CO / 16) * (256 * 16 + 32)) * sizeof(E);
   auto kern = conv3d_wgrad_wide_kernel<MODE, CI, CO, KDN, DY16, CIT, X16>;
   if (smem > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  // tile height 14 where that covers the plane with as many tiles as 16 would (conv3d.hip, conv_tile_h): 56 -> 4 x 14, 28 -> 2 x 14
+  // tile height 14 where that covers the plane with as many tiles as 16 would (conv3d.hip, maavss_conv_tile_h): 56 -> 4 x 14, 28 -> 2 x 14
   const int th = MODE != MODE_F32 ? maavss_conv_tile_h(Ho) : 16;
   const int tiles_x = cdiv(Wo, 16), tiles_y = cdiv(Ho, th);
   const int tiles_total = BT * tiles_x * tiles_y;

@@ -27,7 +27,6 @@
 // the operands exchanged (weights as B), so a lane holds one d column and 16 tokens of a 32-token block, quantises per (d, block)
 // and stores 16 consecutive token bytes of a V^T row.  No quantisation pass, 1 byte per element written instead of 2.
 #include <type_traits>
-#include <stdlib.h>
 #include "mma.h"
 #include "vit_epilogue.h"
 #include "vit_mx.h"
@@ -60,8 +59,8 @@ struct WsArgs {
   MxImages mx;           // epi 3
 };
 
-// SH = MFMA shape: 32 = v_mfma_f32_32x32x16 (rounds 2-3; kept for the MX epilogue and as the measured baseline), 16 = v_mfma_f32_16x16x32
-// (round 4, default).  Same FLOPs per cycle on paper; on RANDOM operands the chip is power-limited and holds a higher clock on the
+// SH = MFMA shape: 16 = v_mfma_f32_16x16x32 (round 4) for every epilogue but the MX one (3), which is built on the accumulator layout of
+// 32 = v_mfma_f32_32x32x16 (rounds 2-3).  Same FLOPs per cycle on paper; on RANDOM operands the chip is power-limited and holds a higher clock on the
 // 16x16x32 form (scripts/valu_probe part 3: 1612 -> 1868 TFLOP/s, +16 %, register-resident f16 loops; both 2470 on zeros), and a
 // 16x16 accumulator gives a lane 8 consecutive output columns of ONE row with the four lanes of a row adjacent: 64 contiguous
 // bytes per row and store instruction instead of 32.
@@ -80,8 +79,7 @@ extern "C" int maavss_ws_stamps_read(unsigned long long* host, int clear) {
 
 template <int EPI, int LN, int MODE, int SH>
 __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
-  static_assert(SH == 32 || SH == 16, "MFMA shape");
-  static_assert(SH == 32 || EPI != 3, "the MX epilogue is built on the 32x32 accumulator layout");
+  static_assert((SH == 32 && EPI == 3) || (SH == 16 && EPI != 3), "MFMA shape: the MX epilogue is built on the 32x32 accumulator layout, every other one on 16x16");
   // LN: 0 none | 1 LayerNorm of the output rows (proj -> norm2) | 2 LayerNorm of the input rows on the way in (norm1 -> qkv) | 3 / 4 = 1 / 2 WITHOUT
   // the affine part (ln_gamma = ln_beta = null: plain (x - mean) * rstd), for callers that fold gamma into the consumer GEMM's frozen weight columns
   // and beta into its bias (W' = W diag(gamma), b' = b + W beta): the deposit of norm1-on-the-way-in then costs two vector instructions per element
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
   constexpr bool LN_POST = LN == 5;
   constexpr bool LN_OUT = LN == 1 || LN == 3, LN_IN = LN == 2 || LN == 4 || LN_POST, AFF = LN == 1 || LN == 2;
   static_assert(LN >= 0 && LN <= 5, "LN variant");
-  static_assert(!LN_POST || (SH == 16 && EPI == 0), "LayerNorm after the product: 16x16x32 form, 16-bit epilogue");
+  static_assert(!LN_POST || EPI == 0, "LayerNorm after the product: 16-bit epilogue");
   static_assert(!LN_OUT || EPI == 2, "LayerNorm of the output rows comes with the residual epilogue");
   static_assert(!LN_IN || EPI == 0 || EPI == 3, "LayerNorm on the way in is wired for the attn.qkv epilogues");
   static_assert(EPI != 3 || LN_IN, "the MX epilogue is wired for attn.qkv (LayerNorm on the way in)");
@@ -296,7 +294,7 @@ __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
   // vector-memory operations of one panel epilogue (loads + stores) that the hand-counted wait may leave in flight.  EPI 3: a
   // half-panel issues 3 (q, k slices: two 8-byte stores + the scale byte) or 2 (v slice: one 16-byte store + the scale byte)
   // (SH = 16 with the LayerNorm output: the 16-bit row goes out as two 8-byte pieces per 16-row block instead of one 16-byte piece)
-  constexpr int S = EPI == 2 ? (LN_OUT ? (SH == 16 && WS16_LN_SPLITCOLS ? 24 : 20) : 16) : 4;
+  constexpr int S = EPI == 2 ? (LN_OUT ? (WS16_LN_SPLITCOLS ? 24 : 20) : 16) : 4;
   int it = 0;
 #ifdef WS_STAMP
   unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime();
@@ -490,7 +488,7 @@ __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
         }
         }   // skip_epi16 (measurement builds)
       } else {
-      // ================= 32x32x16 form (rounds 2-3) =================
+      // ================= 32x32x16 form (rounds 2-3): the MX epilogue =================
       const char* pb = panels_lds + buf * WS_PANEL_BYTES + h2 * (32 * WS_K * 2) + frag_r;
       f32x16 acc;
 #pragma unroll
@@ -498,7 +496,7 @@ __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
         const float4 bq = *reinterpret_cast<const float4*>(bias_lds + wv * 32 + 16 * (q >> 1) + 8 * half + 4 * (q & 1));
         acc[4 * q + 0] = bq.x; acc[4 * q + 1] = bq.y; acc[4 * q + 2] = bq.z; acc[4 * q + 3] = bq.w;
       }
-      if (EPI == 3 && vslice) {   // exchanged operands: this lane's output column is weight row n0 + pi(r32), all 16 registers
+      if (vslice) {   // exchanged operands: this lane's output column is weight row n0 + pi(r32), all 16 registers
         int to = tid;
         asm volatile("" : "+v"(to));
         const int r32o = to & 31;
@@ -507,16 +505,11 @@ __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
         for (int e = 0; e < 16; ++e) acc[e] = bl;
       }
       auto rd = [&](int kb) __attribute__((always_inline)) {
-        // The GELU epilogue makes fc1 vector-ISSUE bound (PMC: 8.5 VALU instructions per MFMA; a 32x32x16 MFMA leaves room for
-        // six): there the eight fragment addresses are precomputed (registers paid for with one step less of read-ahead).  The
-        // other variants have no registers left and recompute the address per read (one v_xad).
         int fx = frag_x;
         asm volatile("" : "+v"(fx));
         return *reinterpret_cast<const bf16x8*>(pb + (((kb & 7) << 5) ^ fx) + (kb >> 3) * 256);
       };
-      // fragment reads kept in flight ahead of the MFMA that consumes them (the residual epilogues are HBM-bound and short of
-      // registers: one)
-      constexpr int WS_DEPTH = (EPI == 2 || EPI == 3) ? 1 : (LN_IN || EPI == 1 || EPI == 4) ? 2 : 3;
+      constexpr int WS_DEPTH = 1;      // fragment reads kept in flight ahead of the MFMA that consumes them (no registers for more)
       auto mfma_loop = [&](auto swapped_c) __attribute__((always_inline)) {
         constexpr bool SWAPPED = decltype(swapped_c)::value;   // C^T = X W^T: lane = output column, registers = rows (EPI 3, v slice)
         bf16x8 f[WS_DEPTH + 1];
@@ -536,124 +529,47 @@ __global__ __launch_bounds__(WS_THREADS) void vit_ws_gemm_kernel(WsArgs g) {
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      if constexpr (EPI == 3) {
-        if (vslice) mfma_loop(std::true_type{});
-        else mfma_loop(std::false_type{});
-      } else {
-        mfma_loop(std::false_type{});
-      }
+      if (vslice) mfma_loop(std::true_type{});
+      else mfma_loop(std::false_type{});
 
       // ---- epilogue: lane (r32, half) holds, of row m0 + 32 h2 + r32, the columns n0 + 16 qp + 8 half + (0..7), qp = 0, 1
-      const int64_t row = m0 + 32 * h2 + r32;
+      // (`row` is not read: the addresses below are rebuilt from an opaque thread index.  It stays declared because hipcc numbers this kernel's
+      // scalar registers differently without it, and the kernel is held to the machine code that was measured)
+      [[maybe_unused]] const int64_t row = m0 + 32 * h2 + r32;
       bool skip_epi = false;
       if constexpr ((abl & 1) != 0) skip_epi = acc[3] != 1234.5f;
       if (!skip_epi) {
-      if constexpr (EPI == 3) {
-        float amax = 0.f;
+      float amax = 0.f;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[e] *= scale; amax = fmaxf(amax, fabsf(acc[e])); }
-        float ma, mb;
-        lane_swap32(amax, ma, mb);
-        float inv;
-        const unsigned eb = mx_scale_byte(fmaxf(ma, mb), inv);
-        unsigned qd[4];
+      for (int e = 0; e < 16; ++e) { acc[e] *= scale; amax = fmaxf(amax, fabsf(acc[e])); }
+      float ma, mb;
+      lane_swap32(amax, ma, mb);
+      float inv;
+      const unsigned eb = mx_scale_byte(fmaxf(ma, mb), inv);
+      unsigned qd[4];
 #pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) qd[q4] = mx_cvt4(acc[4 * q4] * inv, acc[4 * q4 + 1] * inv, acc[4 * q4 + 2] * inv, acc[4 * q4 + 3] * inv);
-        // every per-lane address below is derived from an opaque copy of the thread index: the compiler then cannot hoist them
-        // out of the panel loop into permanently live registers (this kernel has none to spare)
-        int to = tid;
-        asm volatile("" : "+v"(to));
-        const int r32o = to & 31, halfo = (to >> 5) & 1, wvo = to >> 6;
-        if (!vslice) {
-          // lane (row r32, half): columns 16 qp + 8 half + (0..7) of the wave's 32 = dwords (2 qp, 2 qp + 1); scale plane = wv
-          const int64_t rowo = m0 + 32 * h2 + r32o;
-          unsigned char* dst = (slice == 0 ? g.mx.q8 : g.mx.k8) + rowo * MX_DIM + wvo * 32 + 8 * halfo;
-          *reinterpret_cast<uint2*>(dst) = make_uint2(qd[0], qd[1]);
-          *reinterpret_cast<uint2*>(dst + 16) = make_uint2(qd[2], qd[3]);
-          if (halfo == 0) (slice == 0 ? g.mx.sq : g.mx.sk)[(int64_t)wvo * g.mx.rows_alloc + rowo] = (unsigned char)eb;
-        } else {
-          // lane (d column, half): registers (g, i) = token 8 g + 4 half + i of the half panel.  Two lane swaps hand each half 16
-          // CONSECUTIVE tokens: half 0 -> (own q0, other q0, own q1, other q1) = tokens 0..15, half 1 -> tokens 16..31
-          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(qd[0]), "+v"(qd[2]));
-          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(qd[1]), "+v"(qd[3]));
-          const int dcol = wvo * 32 + 16 * (r32o >> 4) + 8 * ((r32o >> 2) & 1) + 4 * ((r32o >> 3) & 1) + (r32o & 3);
-          const int64_t tok0 = m0 + 32 * h2;
-          *reinterpret_cast<uint4*>(g.mx.v8t + (int64_t)dcol * g.mx.rows_alloc + tok0 + 16 * halfo) = make_uint4(qd[0], qd[2], qd[1], qd[3]);
-          if (halfo == 0) g.mx.sv[(tok0 >> 5) * MX_DIM + dcol] = (unsigned char)eb;
-        }
-      } else if constexpr (EPI != 2) {
-        bf16_t* cp = reinterpret_cast<bf16_t*>(g.C) + row * g.ldc + n0 + 8 * half;
-#pragma unroll
-        for (int qp = 0; qp < 2; ++qp) {
-          v2f v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v2f{acc[8 * qp + 2 * e], acc[8 * qp + 2 * e + 1]};
-          if constexpr (EPI == 4) {
-            *reinterpret_cast<uint4*>(cp + 16 * qp) = make_uint4(pg_gelu_h2(v[0]), pg_gelu_h2(v[1]), pg_gelu_h2(v[2]), pg_gelu_h2(v[3]));
-            continue;
-          } else if constexpr (EPI == 1) {
-            pg_gelu4(v[0], v[1]);
-            pg_gelu4(v[2], v[3]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[e].x *= scale; v[e].y *= scale; }
-          }
-          *reinterpret_cast<uint4*>(cp + 16 * qp) = make_uint4(pack2<MODE>(v[0].x, v[0].y), pack2<MODE>(v[1].x, v[1].y),
-                                                                 pack2<MODE>(v[2].x, v[2].y), pack2<MODE>(v[3].x, v[3].y));
-        }
+      for (int q4 = 0; q4 < 4; ++q4) qd[q4] = mx_cvt4(acc[4 * q4] * inv, acc[4 * q4 + 1] * inv, acc[4 * q4 + 2] * inv, acc[4 * q4 + 3] * inv);
+      // every per-lane address below is derived from an opaque copy of the thread index: the compiler then cannot hoist them
+      // out of the panel loop into permanently live registers (this kernel has none to spare)
+      int to = tid;
+      asm volatile("" : "+v"(to));
+      const int r32o = to & 31, halfo = (to >> 5) & 1, wvo = to >> 6;
+      if (!vslice) {
+        // lane (row r32, half): columns 16 qp + 8 half + (0..7) of the wave's 32 = dwords (2 qp, 2 qp + 1); scale plane = wv
+        const int64_t rowo = m0 + 32 * h2 + r32o;
+        unsigned char* dst = (slice == 0 ? g.mx.q8 : g.mx.k8) + rowo * MX_DIM + wvo * 32 + 8 * halfo;
+        *reinterpret_cast<uint2*>(dst) = make_uint2(qd[0], qd[1]);
+        *reinterpret_cast<uint2*>(dst + 16) = make_uint2(qd[2], qd[3]);
+        if (halfo == 0) (slice == 0 ? g.mx.sq : g.mx.sk)[(int64_t)wvo * g.mx.rows_alloc + rowo] = (unsigned char)eb;
       } else {
-        float* cp = reinterpret_cast<float*>(g.C) + row * g.ldc + n0 + 8 * half;
-#pragma unroll
-        for (int qp = 0; qp < 2; ++qp) {     // two 16-byte pieces at a time: the residual epilogues are short of registers
-          const float4 x0 = *reinterpret_cast<const float4*>(cp + 16 * qp), x1 = *reinterpret_cast<const float4*>(cp + 16 * qp + 4);
-          acc[8 * qp + 0] += x0.x; acc[8 * qp + 1] += x0.y; acc[8 * qp + 2] += x0.z; acc[8 * qp + 3] += x0.w;
-          acc[8 * qp + 4] += x1.x; acc[8 * qp + 5] += x1.y; acc[8 * qp + 6] += x1.z; acc[8 * qp + 7] += x1.w;
-          *reinterpret_cast<float4*>(cp + 16 * qp) = make_float4(acc[8 * qp], acc[8 * qp + 1], acc[8 * qp + 2], acc[8 * qp + 3]);
-          *reinterpret_cast<float4*>(cp + 16 * qp + 4) = make_float4(acc[8 * qp + 4], acc[8 * qp + 5], acc[8 * qp + 6], acc[8 * qp + 7]);
-        }
-        if constexpr (LN_OUT) {
-          // LayerNorm of the updated rows: per wave (mean, M2) of its 32 columns of a row (two passes over registers, the two
-          // lane halves combined by a lane swap), the 12 partials of a row merged with the parallel-variance formula.
-          float s = 0.f;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) s += acc[e];
-          float sa, sb;
-          lane_swap32(s, sa, sb);
-          const float mu = (sa + sb) * (1.f / 32.f);
-          float m2 = 0.f;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) { const float d = acc[e] - mu; m2 += d * d; }
-          lane_swap32(m2, sa, sb);
-          // [wave][row]: the 32 rows of a lane group are consecutive 8-byte slots (conflict-free).  The first layout, [row][wave]
-          // with a 24-dword row stride, put rows r and r + 4 on the same banks: every one of these reads was an 8-way conflict,
-          // 48 % of the kernel's LDS cycles (profiles/r3_e_kernel_pmc.json) -- twice the panel's MFMA time on the CU's one LDS.
-          float2* sp = stat_lds + (32 * h2 + r32);
-          if (half == 0) sp[wv * WS_BM] = make_float2(mu, sa + sb);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          float mean = 0.f;
-#pragma unroll 4
-          for (int k = 0; k < WS_WAVES; ++k) mean += sp[k * WS_BM].x;
-          mean *= 1.f / WS_WAVES;
-          float tot = 0.f;
-#pragma unroll 4
-          for (int k = 0; k < WS_WAVES; ++k) { const float2 st = sp[k * WS_BM]; const float d = st.x - mean; tot += st.y + 32.f * d * d; }
-          const float rstd = rsqrtf(tot * (1.f / WS_K) + g.ln_eps);
-          bf16_t* xp = g.XN + row * WS_K + n0 + 8 * half;
-#pragma unroll
-          for (int qp = 0; qp < 2; ++qp) {
-            const int nl = wv * 32 + 16 * qp + 8 * half;
-            unsigned o[4];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              float4 gg = make_float4(1.f, 1.f, 1.f, 1.f), bb = make_float4(0.f, 0.f, 0.f, 0.f);
-              if constexpr (AFF) { gg = *reinterpret_cast<const float4*>(gam_lds + nl + 4 * e); bb = *reinterpret_cast<const float4*>(bet_lds + nl + 4 * e); }
-              o[2 * e] = pack2<MODE>((acc[8 * qp + 4 * e + 0] - mean) * rstd * gg.x + bb.x, (acc[8 * qp + 4 * e + 1] - mean) * rstd * gg.y + bb.y);
-              o[2 * e + 1] = pack2<MODE>((acc[8 * qp + 4 * e + 2] - mean) * rstd * gg.z + bb.z, (acc[8 * qp + 4 * e + 3] - mean) * rstd * gg.w + bb.w);
-            }
-            *reinterpret_cast<uint4*>(xp + 16 * qp) = make_uint4(o[0], o[1], o[2], o[3]);
-          }
-        }
+        // lane (d column, half): registers (g, i) = token 8 g + 4 half + i of the half panel.  Two lane swaps hand each half 16
+        // CONSECUTIVE tokens: half 0 -> (own q0, other q0, own q1, other q1) = tokens 0..15, half 1 -> tokens 16..31
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(qd[0]), "+v"(qd[2]));
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(qd[1]), "+v"(qd[3]));
+        const int dcol = wvo * 32 + 16 * (r32o >> 4) + 8 * ((r32o >> 2) & 1) + 4 * ((r32o >> 3) & 1) + (r32o & 3);
+        const int64_t tok0 = m0 + 32 * h2;
+        *reinterpret_cast<uint4*>(g.mx.v8t + (int64_t)dcol * g.mx.rows_alloc + tok0 + 16 * halfo) = make_uint4(qd[0], qd[2], qd[1], qd[3]);
+        if (halfo == 0) g.mx.sv[(tok0 >> 5) * MX_DIM + dcol] = (unsigned char)eb;
       }
       }   // skip_epi (measurement builds)
       }   // SH
@@ -716,19 +632,13 @@ static int ws_gemm_launch(const char* who, const void* A, const float* X, const 
   const size_t smem = WS_BUFS * WS_PANEL_BYTES + 3 * WS_SLICE * sizeof(float) + WS_BM * WS_WAVES * sizeof(float2);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(8 * cu_per_xcd), block(WS_THREADS);
-  // MFMA shape: 16x16x32 unless MAAVSS_WS_SHAPE=32 asks for the round-2/3 form (A/B runs; read once per process); the MX epilogue is 32x32 only
-  static int shape_env = 0;
-  if (!shape_env) {
-    const char* e = getenv("MAAVSS_WS_SHAPE");
-    shape_env = (e && e[0] == '3') ? 32 : 16;
-  }
+  // MFMA shape: 32x32x16 for the MX epilogue, 16x16x32 for every other
 #define WS_LAUNCH4(E, L, D, H)                                                                                        \
   {                                                                                                                   \
     hipFuncSetAttribute(reinterpret_cast<const void*>(vit_ws_gemm_kernel<E, L, D, H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     hipLaunchKernelGGL((vit_ws_gemm_kernel<E, L, D, H>), grid, block, smem, st, g);                                   \
   }
-#define WS_LAUNCH3(E, L, D) { if (shape_env == 32) WS_LAUNCH4(E, L, D, 32) else WS_LAUNCH4(E, L, D, 16) }
-#define WS_LAUNCH(E, L) { if (dtype == MODE_F16) WS_LAUNCH3(E, L, MODE_F16) else WS_LAUNCH3(E, L, MODE_BF16) }
+#define WS_LAUNCH(E, L) { if (dtype == MODE_F16) WS_LAUNCH4(E, L, MODE_F16, 16) else WS_LAUNCH4(E, L, MODE_BF16, 16) }
   const bool affine = ln_gamma != nullptr;          // null gamma / beta: the LayerNorm variants without the affine part (folded into the consumer's weights)
   if (X && epilogue == 3) {
     if (affine) { if (dtype == MODE_F16) WS_LAUNCH4(3, 2, MODE_F16, 32) else WS_LAUNCH4(3, 2, MODE_BF16, 32) }
@@ -736,9 +646,8 @@ static int ws_gemm_launch(const char* who, const void* A, const float* X, const 
   }
   else if (X && epilogue == 5) { if (dtype == MODE_F16) WS_LAUNCH4(0, 5, MODE_F16, 16) else WS_LAUNCH4(0, 5, MODE_BF16, 16) }
   else if (X && affine) WS_LAUNCH(0, 2) else if (X) WS_LAUNCH(0, 4) else if (epilogue == 0) WS_LAUNCH(0, 0) else if (epilogue == 1) WS_LAUNCH(1, 0)
-  else if (epilogue == 4) WS_LAUNCH3(4, 0, MODE_F16) else if (xn_out && affine) WS_LAUNCH(2, 1) else if (xn_out) WS_LAUNCH(2, 3) else WS_LAUNCH(2, 0)
+  else if (epilogue == 4) WS_LAUNCH4(4, 0, MODE_F16, 16) else if (xn_out && affine) WS_LAUNCH(2, 1) else if (xn_out) WS_LAUNCH(2, 3) else WS_LAUNCH(2, 0)
 #undef WS_LAUNCH4
-#undef WS_LAUNCH3
 #undef WS_LAUNCH
   MAAVSS_LAUNCH_CHECK("vit_ws_gemm_kernel");
   return MAAVSS_OK;

@@ -4,8 +4,6 @@ Tensors are torch CUDA tensors used purely as device-memory handles: every funct
 device pointers + explicit sizes + the current HIP stream to libmaavss_hip.so.  No torch math here.
 Layouts: visual activations channels-last [B,T,H,W,C]; STFT-encoder activations NHWC.
 """
-import os
-
 import torch
 
 from . import _lib
@@ -91,6 +89,11 @@ def wgrad_chunks(b, t, ho, wo, ci=64, co=64):
     return max(1, min(64, tiles // 4))
 
 
+def c1_wgrad_chunks(b, t, h, w):
+    """Number of position chunks of the first-layer (C_in = 1) weight-gradient kernels: one per two 16x16 tiles, at most 1024."""
+    return max(1, min(1024, (b * t * ((h + 15) // 16) * ((w + 15) // 16)) // 2))
+
+
 WGRAD_X16_SHAPES = ((16, 32), (32, 64), (64, 64))      # (C_in, C_out) whose weight-gradient kernel takes a bf16 x (LDS-DMA staging)
 
 
@@ -140,7 +143,7 @@ def conv3d_c1_wgrad(x, dy, dw=None, beta=0, nchunk=None):
     _f32(x, dy, dw)
     b, t, h, wd = x.shape
     if nchunk is None:
-        nchunk = max(1, min(1024, (b * t * ((h + 15) // 16) * ((wd + 15) // 16)) // 2))
+        nchunk = c1_wgrad_chunks(b, t, h, wd)
     ws = torch.empty(nchunk * 1200, device=x.device, dtype=torch.float32)
     if dw is None:
         dw = torch.empty(16, 1, 3, 5, 5, device=x.device, dtype=torch.float32)
@@ -155,8 +158,7 @@ def conv3d_c1_wgrad_bn(x, y, dout, out, arg, mean, invstd, coef, pool, dw=None, 
     b, t, h, wd = x.shape
     assert y.shape == (b, t, h, wd, 16) and dout.is_contiguous() and out.is_contiguous()
     if nchunk is None:
-        cap = int(os.environ.get("MAAVSS_C1_NCHUNK", "1024"))
-        nchunk = max(1, min(cap, (b * t * ((h + 15) // 16) * ((wd + 15) // 16)) // 2))
+        nchunk = c1_wgrad_chunks(b, t, h, wd)
     ws = torch.empty(nchunk * 1200, device=x.device, dtype=torch.float32)
     if dw is None:
         dw, beta = torch.empty(16, 1, 3, 5, 5, device=x.device, dtype=torch.float32), 0
@@ -198,8 +200,7 @@ def conv3d_c1_wgrad_bn_recompute(x, w, dout, arg, mean, invstd, bn_beta, coef, p
     b, t, h, wd = x.shape
     assert dout.is_contiguous() and w.is_contiguous()
     if nchunk is None:
-        cap = int(os.environ.get("MAAVSS_C1_NCHUNK", "1024"))
-        nchunk = max(1, min(cap, (b * t * ((h + 15) // 16) * ((wd + 15) // 16)) // 2))
+        nchunk = c1_wgrad_chunks(b, t, h, wd)
     ws = torch.empty(nchunk * 1200, device=x.device, dtype=torch.float32)
     if dw is None:
         dw, beta = torch.empty(16, 1, 3, 5, 5, device=x.device, dtype=torch.float32), 0

@@ -212,11 +212,6 @@ class VideoAttention:
         self.checkpoint_key = "teacher"
         self.device = torch.device(device)
         self.frames_per_launch = frames_per_launch
-        self.fused_panel_gemm = os.environ.get("MAAVSS_VIT_PANEL_GEMM", "1") != "0"   # LN+GEMM panel kernel for K=384
-        # K = 384 layers on the weight-stationary kernel (maavss_vit_ws_gemm): norm1 applied while qkv loads x (row statistics
-        # from the kernels that wrote x), norm2 written by proj
-        self.ws_gemm = os.environ.get("MAAVSS_VIT_WS_GEMM", "1") != "0"
-        self.ws_ln_in = os.environ.get("MAAVSS_VIT_WS_LN", "1") != "0"     # measurement switch: 0 = norm1 as its own pass
         self.model = self.__load_model(path_to_weights)
         self._dev = None          # device-side weight images, built lazily
         self._tables = {}
@@ -294,13 +289,14 @@ class VideoAttention:
         rows = f * ntok
         dev, st, dt, tdt = frames.device, stream_ptr(), self.dt, _TORCH_DT[self.dt]
         wts, table = self._device_weights(), self._row_table(hp, wp)
-        rpad = (rows + 127) // 128 * 128      # the panel GEMM stores whole 128-row panels (include/maavss.h)
+        # maavss_vit_ws_gemm reads and stores whole 64-row panels: its operands need ceil(rows / 64) * 64 allocated rows (include/maavss.h)
+        rpad = (rows + 127) // 128 * 128
         a = torch.empty(rows, 192, device=dev, dtype=tdt)
         x = torch.empty(rpad, DIM, device=dev, dtype=torch.float32)
-        xn = torch.empty(rpad, DIM, device=dev, dtype=tdt) if (self.ws_gemm or not self.fused_panel_gemm) else None
+        xn = torch.empty(rpad, DIM, device=dev, dtype=tdt)
         # per-row LayerNorm partials of x over its three 128-column thirds, written by the kernels that store x (patch
         # embedding, fc2) and merged by the qkv kernel, which normalises x on the way in: norm1 never runs as a pass
-        stats = torch.empty(rows, 3, 2, device=dev, dtype=torch.float32) if self.ws_gemm else None
+        stats = torch.empty(rows, 3, 2, device=dev, dtype=torch.float32)
         qkv = torch.empty(rpad, 3 * DIM, device=dev, dtype=tdt)
         att_o = torch.empty(rpad, DIM, device=dev, dtype=tdt)
         hid = torch.empty(rpad, MLP, device=dev, dtype=tdt)
@@ -320,67 +316,38 @@ class VideoAttention:
             att_o[rows:].zero_()
         call("maavss_vit_patchify", ptr(frames), ptr(a), f, h, w, dt, st)
         call("maavss_vit_gemm_stats", ptr(a), 192, ptr(wts["patch_w"]), None, ptr(table), ntok, ptr(x), DIM, rows, DIM, 192,
-             EPI_F32_ROWTABLE, 0, 1.0, ptr(stats) if (self.ws_gemm and self.ws_ln_in) else None, dt, st)
+             EPI_F32_ROWTABLE, 0, 1.0, ptr(stats), dt, st)
         qs = 0.125 * 1.4426950408889634          # q *= log2(e)/sqrt(64): the attention kernels run softmax on exp2
         for i in range(DEPTH):
             b = wts[i]
             # the last block only feeds the CLS-row attention (get_last_selfattention): q and k, not v -- the weight rows
             # are [q; k; v], so N = 2 DIM computes exactly those two thirds into the same [rows, 3 DIM] buffer
             nqkv = 2 * DIM if i == DEPTH - 1 else 3 * DIM
-            fp8_here = self.attn_fp8 and i in self.fp8_blocks
-            mx_fused = fp8_here and self.ws_gemm and self.ws_ln_in and i < DEPTH - 1
-            if mx_fused:
-                # norm1 + qkv -> block-scaled fp8 operand images, no 16-bit qkv tensor and no quantisation pass
+            fp8_here = i in self.fp8_blocks          # (never the last block)
+            # norm1 + qkv: weights stationary in registers, x normalised on its way into LDS (row statistics from the kernel that wrote x)
+            if fp8_here:
+                # -> block-scaled fp8 operand images, no 16-bit qkv tensor and no quantisation pass
                 call("maavss_vit_ws_gemm_ln_mx", ptr(x), rpad, ptr(stats), ptr(b["n1w"]), ptr(b["n1b"]), LN_EPS, ptr(b["qkv_w"]),
                      ptr(b["qkv_b"]), ptr(ws8), rows, DIM, qs, dt, st)
-            elif self.ws_gemm:
-                if not self.ws_ln_in:
-                    call("maavss_vit_layernorm", ptr(x), ptr(b["n1w"]), ptr(b["n1b"]), ptr(xn), rows, DIM, LN_EPS, dt, st)
-                    call("maavss_vit_ws_gemm", ptr(xn), DIM, rpad, ptr(b["qkv_w"]), ptr(b["qkv_b"]), ptr(qkv), 3 * DIM, rpad, rows, nqkv,
-                         EPI_BF16_BIAS, DIM, qs, None, None, None, LN_EPS, dt, st)
-                else:
-                  # norm1 + qkv: weights stationary in registers, x normalised on its way into LDS
-                  if self.qkv_ln == "post":
-                      call("maavss_vit_ws_gemm_ln_post", ptr(x), rpad, ptr(stats), ptr(b["qkv_cs"]), LN_EPS, ptr(b["qkv_wf"]), ptr(b["qkv_bf"]),
-                           ptr(qkv), 3 * DIM, rpad, rows, nqkv, DIM, qs, dt, st)
-                  else:
-                      call("maavss_vit_ws_gemm_ln", ptr(x), rpad, ptr(stats), ptr(b["n1w"]), ptr(b["n1b"]), LN_EPS, ptr(b["qkv_w"]),
-                           ptr(b["qkv_b"]), ptr(qkv), 3 * DIM, rpad, rows, nqkv, DIM, qs, dt, st)
-            elif self.fused_panel_gemm:
-                # norm1 + qkv in one kernel (activation panel stationary in LDS, LayerNorm on the way in)
-                call("maavss_vit_panel_gemm", ptr(x), None, 0, ptr(b["n1w"]), ptr(b["n1b"]), LN_EPS, ptr(b["qkv_w"]),
-                     ptr(b["qkv_b"]), ptr(qkv), 3 * DIM, rpad, rows, nqkv, EPI_BF16_BIAS, DIM, qs, dt, st)
+            elif self.qkv_ln == "post":
+                call("maavss_vit_ws_gemm_ln_post", ptr(x), rpad, ptr(stats), ptr(b["qkv_cs"]), LN_EPS, ptr(b["qkv_wf"]), ptr(b["qkv_bf"]),
+                     ptr(qkv), 3 * DIM, rpad, rows, nqkv, DIM, qs, dt, st)
             else:
-                call("maavss_vit_layernorm", ptr(x), ptr(b["n1w"]), ptr(b["n1b"]), ptr(xn), rows, DIM, LN_EPS, dt, st)
-                call("maavss_vit_gemm", ptr(xn), DIM, ptr(b["qkv_w"]), ptr(b["qkv_b"]), None, 0, ptr(qkv), 3 * DIM, rows,
-                     nqkv, DIM, EPI_BF16_BIAS, DIM, qs, dt, st)
+                call("maavss_vit_ws_gemm_ln", ptr(x), rpad, ptr(stats), ptr(b["n1w"]), ptr(b["n1b"]), LN_EPS, ptr(b["qkv_w"]),
+                     ptr(b["qkv_b"]), ptr(qkv), 3 * DIM, rpad, rows, nqkv, DIM, qs, dt, st)
             if i == DEPTH - 1:
                 break
             if fp8_here:
-                if not mx_fused:
-                    call("maavss_vit_qkv_mx", ptr(qkv), ptr(ws8), rows, 3 * DIM, dt, st)
                 call("maavss_vit_attn_mx", ptr(ws8), ptr(att_o), f, ntok, HEADS, DIM, dt, st)
             else:
                 call("maavss_vit_attn", ptr(qkv), ptr(att_o), f, ntok, HEADS, 3 * DIM, DIM, dt, st)
-            if self.ws_gemm:
-                # proj adds into the residual stream and writes norm2 of the updated rows; fc1 reads that
-                call("maavss_vit_ws_gemm", ptr(att_o), DIM, rpad, ptr(b["proj_w"]), ptr(b["proj_b"]), ptr(x), DIM, rpad, rows, DIM,
-                     EPI_F32_BIAS_RESID, 0, 1.0, ptr(xn), ptr(b["n2w"]), ptr(b["n2b"]), LN_EPS, dt, st)
-                call("maavss_vit_ws_gemm", ptr(xn), DIM, rpad, ptr(b["fc1_w"]), ptr(b["fc1_b"]), ptr(hid), MLP, rpad, rows, MLP,
-                     self.gelu_epilogue, 0, 1.0, None, None, None, LN_EPS, dt, st)
-            elif self.fused_panel_gemm:
-                call("maavss_vit_panel_gemm", None, ptr(att_o), DIM, None, None, LN_EPS, ptr(b["proj_w"]), ptr(b["proj_b"]),
-                     ptr(x), DIM, rpad, rows, DIM, EPI_F32_BIAS_RESID, 0, 1.0, dt, st)
-                call("maavss_vit_panel_gemm", ptr(x), None, 0, ptr(b["n2w"]), ptr(b["n2b"]), LN_EPS, ptr(b["fc1_w"]),
-                     ptr(b["fc1_b"]), ptr(hid), MLP, rpad, rows, MLP, EPI_BF16_BIAS_GELU, 0, 1.0, dt, st)
-            else:
-                call("maavss_vit_gemm", ptr(att_o), DIM, ptr(b["proj_w"]), ptr(b["proj_b"]), None, 0, ptr(x), DIM, rows,
-                     DIM, DIM, EPI_F32_BIAS_RESID, 0, 1.0, dt, st)
-                call("maavss_vit_layernorm", ptr(x), ptr(b["n2w"]), ptr(b["n2b"]), ptr(xn), rows, DIM, LN_EPS, dt, st)
-                call("maavss_vit_gemm", ptr(xn), DIM, ptr(b["fc1_w"]), ptr(b["fc1_b"]), None, 0, ptr(hid), MLP, rows, MLP,
-                     DIM, EPI_BF16_BIAS_GELU, 0, 1.0, dt, st)
+            # proj adds into the residual stream and writes norm2 of the updated rows; fc1 reads that
+            call("maavss_vit_ws_gemm", ptr(att_o), DIM, rpad, ptr(b["proj_w"]), ptr(b["proj_b"]), ptr(x), DIM, rpad, rows, DIM,
+                 EPI_F32_BIAS_RESID, 0, 1.0, ptr(xn), ptr(b["n2w"]), ptr(b["n2b"]), LN_EPS, dt, st)
+            call("maavss_vit_ws_gemm", ptr(xn), DIM, rpad, ptr(b["fc1_w"]), ptr(b["fc1_b"]), ptr(hid), MLP, rpad, rows, MLP,
+                 self.gelu_epilogue, 0, 1.0, None, None, None, LN_EPS, dt, st)
             call("maavss_vit_gemm_stats", ptr(hid), MLP, ptr(b["fc2_w"]), ptr(b["fc2_b"]), None, 0, ptr(x), DIM, rows, DIM, MLP,
-                 EPI_F32_BIAS_RESID, 0, 1.0, ptr(stats) if (self.ws_gemm and self.ws_ln_in) else None, dt, st)
+                 EPI_F32_BIAS_RESID, 0, 1.0, ptr(stats), dt, st)
         att = torch.empty(f, HEADS, ntok - 1, device=dev, dtype=torch.float32)
         call("maavss_vit_cls_attn", ptr(qkv), ptr(att), f, ntok, HEADS, 3 * DIM, dt, st)
         return att
