@@ -1,5 +1,5 @@
 // K8 (weight gradient), wide variant for the two large-M layers (Conv3d 16->32 and 32->64, reference
-// avse_model_final.py:39,44).  The first wgrad kernel (conv3d.hip) gives every (kd,kh) its own workgroup, so each
+// avse_model_final.py:39,44).  The narrow wgrad kernel (conv3d_wgrad.hip) gives every (kd,kh) its own workgroup, so each
 // x / dy tile is pulled through L2 fifteen times (measured 14.3 GB fetched per launch for 16->32, MFMA busy 2 %).
 // Here one 512-thread workgroup owns KDN*25 taps: all 75 taps for 16->32 (KDN = 3), one kd for 32->64 (KDN = 1),
 // so a tile is staged once (resp. 3 times) and the 25..75 tap products run from the same LDS image:
@@ -7,7 +7,7 @@
 // with the position as the MFMA K dimension, both operands read transposed from channels-last LDS tiles by
 // ds_read_b64_tr_b16.  Output: the same partial layout as the first kernel ([chunk][tap][ci][co]) for the common
 // deterministic reduce kernel.
-#include "mma.h"
+#include "conv3d_tile.h"
 
 #ifndef WG_DEPTH
 #define WG_DEPTH 3      // X16: (tap, channel block) pairs whose x fragments are read ahead of the MFMAs
@@ -311,8 +311,6 @@ __global__ __launch_bounds__(512) void conv3d_wgrad_wide_kernel(const float* __r
   }
 }
 
-int maavss_conv_tile_h(int Ho);      // conv3d.hip
-
 template <int MODE, int CI, int CO, int KDN, bool DY16 = false, int CIT = CI, bool X16 = false>
 static void launch_wide(const float* x, const void* dy, float* ws, int BT, int T, int H, int W, int Ho, int Wo, int pad,
                         int nchunk, hipStream_t st) {
@@ -322,7 +320,7 @@ static void launch_wide(const float* x, const void* dy, float* ws, int BT, int T
                                    : (size_t)(KDN * (CI / 16) * (400 * 16 + 32) + (CO / 16) * (256 * 16 + 32)) * sizeof(E);
   auto kern = conv3d_wgrad_wide_kernel<MODE, CI, CO, KDN, DY16, CIT, X16>;
   if (smem > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  // tile height 14 where that covers the plane with as many tiles as 16 would (conv3d.hip, maavss_conv_tile_h): 56 -> 4 x 14, 28 -> 2 x 14
+  // tile height 14 where that covers the plane with as many tiles as 16 would (conv3d_tile.h, maavss_conv_tile_h): 56 -> 4 x 14, 28 -> 2 x 14
   const int th = MODE != MODE_F32 ? maavss_conv_tile_h(Ho) : 16;
   const int tiles_x = cdiv(Wo, 16), tiles_y = cdiv(Ho, th);
   const int tiles_total = BT * tiles_x * tiles_y;

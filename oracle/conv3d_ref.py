@@ -33,7 +33,7 @@ def c1_tiles(b, t, h, w):
 
 
 # The MFMA first layer's workgroups walk 8 tiles each and write one partial row per workgroup: `#define C1_TPW 8` in
-# csrc/conv3d.hip, restated by hand (the check that matters is the exact sum of the partial rows, not this count).
+# csrc/conv3d_c1.hip, restated by hand (the check that matters is the exact sum of the partial rows, not this count).
 C1_TILES_PER_WG = 8
 
 

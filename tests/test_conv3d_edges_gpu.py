@@ -1,4 +1,4 @@
-"""The Conv3d(3,5,5) kernels (csrc/conv3d.hip, csrc/conv3d_wgrad_wide.hip) at their tile edges, against float64 references.
+"""The Conv3d(3,5,5) kernels (csrc/conv3d_igemm.hip, conv3d_wgrad.hip, conv3d_wgrad_wide.hip, conv3d_c1.hip) at their tile edges, against float64 references.
 
 Most cases are integer-exact: operands are small integers, so every product and partial sum is an integer below 2^24 in any
 summation order and the f32, bf16 and IEEE-half paths must all return the float64 result bit for bit (torch.equal, no
