@@ -34,8 +34,9 @@ extern "C" {
  *   400  round 4: maavss_set_deterministic_workspace takes the stream the scratch is bound to; NULL ln_gamma / ln_beta = LayerNorm without
  *        the affine part; epilogue 4 of maavss_vit_ws_gemm (GELU in packed half); the in-kernel noise of maavss_stft_fwd draws the bin n_fft / 2
  *        from its own per-frame-pair Philox block (same seed, different noise in that bin); maavss_bn_pool_act_fwd and
- *        maavss_conv3d_c1_bn_pool_act take an out_bf16 pointer behind out16, maavss_conv3d_wgrad's dy16 became the mask in16; see INTEGRATION.md */
-#define MAAVSS_ABI_VERSION 400
+ *        maavss_conv3d_c1_bn_pool_act take an out_bf16 pointer behind out16, maavss_conv3d_wgrad's dy16 became the mask in16; see INTEGRATION.md
+ *   401  maavss_convt2d_{out_size,fwd,dgrad,wgrad_nchunk,wgrad} removed: the STFT decoder runs through maavss_conv2d_gen_* (<= 30 taps) */
+#define MAAVSS_ABI_VERSION 401
 const char* maavss_last_error(void);
 int maavss_version(void);
 const char* maavss_arch(void);
@@ -204,22 +205,9 @@ int maavss_conv2d_wgrad_nchunk(int B, int Ho, int Wo, int Ci, int Co);
 int maavss_conv2d_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int Ci, int H, int W, int Co,
                         int sh, int sw, int pw, int in_layout, int beta, void* stream);
 
-/* ---- K11 ConvTranspose2d(k=(3,kw), kw in {9,10}, stride (sh,sw), padding (1,4), output_padding (oph,opw), bias=False)
- * -- the STFT decoder, avse_model_final.py:155-193 (audio_ae_forward :254-256) ----
- * x / dx NHWC [B][Hi][Wi][Ci]; w [Ci][Co][3][kw] (reference layout); y / dy [B][Ho][Wo][Co] for out_layout 1 or the
- * network's NCHW [B][Co][Ho][Wo] for out_layout 0 (last decoder layer); Ho = (Hi-1) sh + 1 + oph, Wo = (Wi-1) sw - 8 + kw + opw.
- * wgrad ws: maavss_convt2d_wgrad_nchunk(B,Hi,Wi) * Ci*Co*3*kw floats; beta 1 accumulates into dw. */
-int maavss_convt2d_out_size(int Hi, int Wi, int kw, int sh, int sw, int oph, int opw, int* Ho, int* Wo);
-int maavss_convt2d_fwd(const float* x, const float* w, float* y, int B, int Ci, int Hi, int Wi, int Co, int kw, int sh, int sw,
-                       int oph, int opw, int out_layout, void* stream);
-int maavss_convt2d_dgrad(const float* dy, const float* w, float* dx, int B, int Ci, int Hi, int Wi, int Co, int kw, int sh,
-                         int sw, int oph, int opw, int out_layout, void* stream);
-int maavss_convt2d_wgrad_nchunk(int B, int Hi, int Wi);
-int maavss_convt2d_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int Ci, int Hi, int Wi, int Co, int kw,
-                         int sh, int sw, int oph, int opw, int out_layout, int beta, void* stream);
-
-/* ---- K19 generic biased Conv2d / ConvTranspose2d of the phasegram variant avse_model.AV_Fusion_Model
- * (avse_model.py:433,452,494,591): kernels (1,9) and (5,5), any stride / padding, <= 25 taps.
+/* ---- K19 generic Conv2d / ConvTranspose2d (bias nullable) of the phasegram variant avse_model.AV_Fusion_Model
+ * (avse_model.py:433,452,494,591): kernels (1,9) and (5,5), any stride / padding, <= 30 taps, also the
+ * STFT decoder (avse_model_final.py:155-193: ConvTranspose2d (3,9) / (3,10), padding (1,4), bias=False; formerly K11).
  * A small map S [B][Hs][Ws][Cs] and a big map G [B][Hb][Wb][Cb] with by = sy*sh - ph + kh, bx = sx*sw - pw + kw and a
  * weight w[cs][cb][kh][kw] (= Conv2d's [Co][Ci] and ConvTranspose2d's [Ci][Co]):
  *   gen_small: S = bias + G (*) w   -- Conv2d forward, ConvTranspose2d input gradient (bias NULL)

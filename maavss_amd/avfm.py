@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .avse import _bn_eval_reduce
+from ._engine import (bilstm_dseq, bilstm_fwd, bilstm_wgrad_operands, bn_eval_reduce, bn_stats_padded, cpad, mark_touched,
+                      pad_c)
 
 FUSED_DIM, LSTM_HIDDEN, SLOPE = 512, 256, 0.3
 
@@ -76,11 +77,6 @@ def _plan_stft_decoder(t_a, n_bins, h, w_enc, latent, c_stft):
     return plan
 
 
-def _cpad(c):
-    """channel count the BatchNorm kernels accept (power of two >= 4) -- all counts here are powers of two already."""
-    return max(c, 4)
-
-
 class _Fn(torch.autograd.Function):
     """One autograd node per entry point (forward / visual_ae_forward / audio_ae_forward)."""
 
@@ -102,9 +98,7 @@ class _Fn(torch.autograd.Function):
         finally:
             model._bn_eval = False
         ctx.saved = None
-        flat = getattr(model, "_maavss_flat", None)
-        if flat is not None:      # FusedAdam steps only parameters that received a gradient (torch.optim.Adam semantics)
-            flat.mark(n for n in names if grads.get(n) is not None)
+        mark_touched(model, grads)
         return (None, None) + (None,) * ctx.n_in + tuple(grads.get(n) for n in names)
 
 
@@ -137,15 +131,13 @@ class _FusionFn(torch.autograd.Function):
         d_a = d_v = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             b, h, w, cv, ca = sv["seq"].shape[0], model.h, model.w_enc, model.c_v, model.c_a
-            dseq = model._fusion_dseq(dgx).view(b, h, (cv + ca) * w)
+            dseq = bilstm_dseq(dgx, model.lstm).view(b, h, (cv + ca) * w)
             if ctx.needs_input_grad[2]:
                 d_v = dseq[:, :, :cv * w].reshape(b, h, cv, w).permute(0, 2, 1, 3)
             if ctx.needs_input_grad[1]:
                 d_a = dseq[:, :, cv * w:].reshape(b, h, ca, w).permute(0, 2, 1, 3)
         ctx.saved = None
-        flat = getattr(model, "_maavss_flat", None)
-        if flat is not None:
-            flat.mark(n for n in _FUSION_PARAMS if grads.get(n) is not None)
+        mark_touched(model, grads)
         return (None, d_a, d_v) + tuple(grads.get(n) for n in _FUSION_PARAMS)
 
 
@@ -262,25 +254,6 @@ class AV_Fusion_Model(nn.Module):
         conv = seq[layer["idx"]]
         return conv, (seq[layer["idx"] + 1] if layer["bn"] else None)
 
-    def _bn_stats(self, y, bn, c, count, train):
-        cp = y.shape[-1]
-        if cp == c:
-            rm, rv = bn.running_mean, bn.running_var
-        else:
-            z = torch.zeros(cp - c, device=y.device, dtype=torch.float32)
-            rm, rv = torch.cat((bn.running_mean, z)), torch.cat((bn.running_var, z + 1))
-        if not train:
-            return ops.bn_eval_stats(rm, rv, bn.eps)
-        mean, invstd = ops.bn_finalize(ops.bn_stats(y, cp), count, rm, rv, bn.num_batches_tracked, bn.eps, bn.momentum)
-        if cp != c:
-            bn.running_mean.copy_(rm[:c])
-            bn.running_var.copy_(rv[:c])
-        return mean, invstd
-
-    @staticmethod
-    def _pad1(t, cp):
-        return t if t.shape[0] == cp else torch.cat((t, torch.zeros(cp - t.shape[0], device=t.device, dtype=t.dtype)))
-
     def _stack_forward(self, name, x_map, train, final_nchw=False, seq_out=None):
         """x_map: ops.Map of the input.  Runs conv(+bias) -> BN -> tanh per layer.  `seq_out` = (buffer, element offset,
         strides) makes the last layer's BN+tanh write straight into the LSTM sequence buffer.  Returns (output, saved)."""
@@ -304,7 +277,7 @@ class AV_Fusion_Model(nn.Module):
                 y = torch.empty(b, co, ho, wo, device=cur.t.device, dtype=torch.float32)
                 ymap = ops.Map(y, nchw=True)
             else:
-                cp = _cpad(co) if bn is not None else co
+                cp = cpad(co) if bn is not None else co
                 y = torch.zeros(b, ho, wo, cp, device=cur.t.device, dtype=torch.float32) if cp != co else \
                     torch.empty(b, ho, wo, cp, device=cur.t.device, dtype=torch.float32)
                 ymap = ops.Map(y, c=co)
@@ -315,8 +288,8 @@ class AV_Fusion_Model(nn.Module):
             rec = dict(x=cur, y=ymap)
             if bn is not None:
                 cp = y.shape[-1]
-                mean, invstd = self._bn_stats(y, bn, co, b * ho * wo, train)
-                gamma, beta = self._pad1(bn.weight.detach(), cp), self._pad1(bn.bias.detach(), cp)
+                mean, invstd = bn_stats_padded(y, bn, co, b * ho * wo, train)
+                gamma, beta = pad_c(bn.weight.detach(), cp), pad_c(bn.bias.detach(), cp)
                 y5 = y.view(b, ho, 1, wo, cp)                   # "T" = rows, one spatial row each: strides per row / column
                 if last and seq_out is not None:
                     buf, off, strides = seq_out
@@ -356,7 +329,7 @@ class AV_Fusion_Model(nn.Module):
                     dout, out = dcur.view(s["y5"].shape), s["out"]
                 dy = ops.bn_pool_act_bwd(dout, out, None, s["y5"], s["mean"], s["invstd"], s["gamma"], 1, ops.BN_TANH,
                                          strides=s["strides"], dgamma=gw, dbeta=gb,
-                                         reduce_fn=_bn_eval_reduce if getattr(self, "_bn_eval", False) else None)
+                                         reduce_fn=bn_eval_reduce if getattr(self, "_bn_eval", False) else None)
                 if need.get(f"{prefix}.{idx + 1}.weight", False):
                     grads[f"{prefix}.{idx + 1}.weight"] = gw[:ymap.c].clone()
                 if need.get(f"{prefix}.{idx + 1}.bias", False):
@@ -418,12 +391,8 @@ class AV_Fusion_Model(nn.Module):
         """av_fusion_forward (avse_model.py:658-670) on the sequence buffer seq [B, h, (c_v + c_a) * w]: BiLSTM over the h
         phasegram rows, fc1 + bias + LeakyReLU(0.3), fc2 + bias + LeakyReLU(0.3)."""
         pr = ops.MODE_F32
-        b, h, feat = seq.shape
-        seq2d = seq.view(b * h, feat)
-        gx = torch.empty(b * h, 2048, device=seq.device, dtype=torch.float32)
-        ops.gemm(seq2d, self.lstm.weight_ih_l0.detach(), out=gx[:, :1024], precise=pr, split_k=1)
-        ops.gemm(seq2d, self.lstm.weight_ih_l0_reverse.detach(), out=gx[:, 1024:], precise=pr, split_k=1)
-        av, hp, gs, cs = ops.lstm_fwd(gx.view(b, h, 2, 4, 256), self.lstm.weight_hh_l0.detach(), self.lstm.weight_hh_l0_reverse.detach())
+        b, h = seq.shape[0], seq.shape[1]
+        av, hp, gs, cs = bilstm_fwd(seq, self.lstm)
         h1 = ops.bias_act_(ops.gemm(av.view(b, h * 512), self.fc1.weight.detach(), precise=pr), self.fc1.bias.detach(), ops.ACT_LEAKY, SLOPE)
         fused = ops.bias_act_(ops.gemm(h1, self.fc2.weight.detach(), precise=pr), self.fc2.bias.detach(), ops.ACT_LEAKY, SLOPE)
         sv.update(seq=seq, av=av, hp=hp, gs=gs, cs=cs, h1=h1, fused=fused)
@@ -449,18 +418,10 @@ class AV_Fusion_Model(nn.Module):
         dav = ops.gemm(dz1, self.fc1.weight.detach(), trans_b=True, precise=pr)
         dgx = ops.lstm_bwd(dav.view(b, h, 512), self.lstm.weight_hh_l0.detach(), self.lstm.weight_hh_l0_reverse.detach(),
                            sv["gs"], sv["cs"]).view(b * h, 2048)
-        seq2d, hp2 = sv["seq"].view(b * h, -1), sv["hp"].view(b * h, 512)
-        for nm, dz, x in (("lstm.weight_ih_l0", dgx[:, :1024], seq2d), ("lstm.weight_ih_l0_reverse", dgx[:, 1024:], seq2d),
-                          ("lstm.weight_hh_l0", dgx[:, :1024], hp2[:, :256]), ("lstm.weight_hh_l0_reverse", dgx[:, 1024:], hp2[:, 256:])):
+        for nm, dz, x in bilstm_wgrad_operands(dgx, sv["seq"], sv["hp"]):
             if need.get(nm, False):
                 grads[nm] = ops.gemm(dz, x, trans_a=True, trans_b=True, precise=pr)
         return dgx
-
-    def _fusion_dseq(self, dgx):
-        pr = ops.MODE_F32
-        dseq = ops.gemm(dgx[:, :1024], self.lstm.weight_ih_l0.detach(), trans_b=True, precise=pr)
-        ops.gemm(dgx[:, 1024:], self.lstm.weight_ih_l0_reverse.detach(), trans_b=True, out=dseq, beta=1, precise=pr)
-        return dseq
 
     def _run_backward(self, mode, sv, d_outs, need):
         grads = {}
@@ -503,7 +464,7 @@ class AV_Fusion_Model(nn.Module):
         enc_need = any(need.get(n, False) for n in self._names["full"] if n.startswith(("phasegram_encoder.", "stft_encoder.")))
         if not enc_need:
             return grads
-        dseq = self._fusion_dseq(dgx)
+        dseq = bilstm_dseq(dgx, self.lstm)
         flat_d, flat_o = dseq.view(-1), sv["seq"].view(-1)
         self._stack_backward("pgram_enc", sv["s_v"], None, need, grads, dcur_strided=(flat_d, flat_o))
         off = self.c_v * w

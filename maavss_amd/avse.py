@@ -24,6 +24,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from ._engine import (bilstm_dseq, bilstm_fwd, bilstm_wgrad_operands, bn_eval_reduce, bn_stats_padded, cpad, mark_touched,
+                      pad_c)
 
 LSTM_HIDDEN = 256
 FUSED_DIM = 512
@@ -82,20 +84,22 @@ def stft_decoder_plan(t_a, n_bins, t_v, s_v, latent, c_stft):
     return plan
 
 
-def _bn_eval_reduce(sums):
-    """BatchNorm backward for a forward that used RUNNING statistics: mean and variance do not depend on the batch, so
-    dy = gamma * invstd * g without the batch-mean terms.  The split backward (ops.bn_pool_act_bwd with `reduce_fn`) takes the
-    dx coefficients from this [2C + 1] vector (sum g, sum g * xhat, count) and dgamma / dbeta from the untouched local copy:
-    zeroing the two sums is the eval-mode formula."""
-    sums[:-1].zero_()
-    return sums
+def _bn_train_stats(part, count, bn, sync):
+    """training-mode (mean, invstd) from the partial sums; `sync` (set_bn_sync) all-reduces them over the data-parallel ranks"""
+    if sync is None:
+        return ops.bn_finalize(part, count, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum)
+    return ops.bn_finalize_synced(part, count, sync, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum)
 
 
-def _mark_touched(model, grads):
-    """tell a FusedAdam built on this model which parameters just received a gradient (torch.optim.Adam skips the rest)"""
-    flat = getattr(model, "_maavss_flat", None)
-    if flat is not None:
-        flat.mark(n for n, g in grads.items() if g is not None)
+def _bn_grad_bufs(prefix, idx, need, gbuf, out_grads):
+    """(dgamma buffer, dbeta buffer, accumulate) of BatchNorm module `prefix.idx`, entered in out_grads -- or (None, None, False)"""
+    nw, nb = f"{prefix}.{idx}.weight", f"{prefix}.{idx}.bias"
+    if not (need.get(nw, False) or need.get(nb, False)):
+        return None, None, False
+    gw, beta = gbuf(nw)
+    gb, _ = gbuf(nb)
+    out_grads[nw], out_grads[nb] = gw, gb
+    return gw, gb, bool(beta)
 
 
 class _AVSEFunction(torch.autograd.Function):
@@ -116,7 +120,7 @@ class _AVSEFunction(torch.autograd.Function):
         # backward has no batch-mean terms (torch autograd allows this; fine-tuning with frozen statistics)
         grads = model._engine_backward(ctx.saved, d_a, d_v, d_fused, need, bn_eval=not ctx.was_training)
         ctx.saved = None
-        _mark_touched(model, grads)
+        mark_touched(model, grads)
         return (None, None, None) + tuple(grads.get(n) for n in names)
 
 
@@ -152,11 +156,11 @@ class _FusionFunction(torch.autograd.Function):
         d_a = d_v = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             b, ts = ctx.shape[0], model.t_v * model.s_v
-            dseq = model._fusion_dseq(dgx, b)
+            dseq = bilstm_dseq(dgx, model.lstm).view(b, model.latent_channels, -1)
             d_v = dseq[:, :, :ts].reshape(ctx.shape) if ctx.needs_input_grad[2] else None
             d_a = dseq[:, :, ts:].reshape(ctx.shape) if ctx.needs_input_grad[1] else None
         ctx.saved = None
-        _mark_touched(model, grads)
+        mark_touched(model, grads)
         return (None, d_a, d_v) + tuple(grads.get(n) for n in _FUSION_PARAMS)
 
 
@@ -174,8 +178,7 @@ class _AEFunction(torch.autograd.Function):
         model = ctx.model
         grads = model._ae_backward(ctx.saved, d_out.contiguous().float(), bn_eval=not ctx.was_training)
         ctx.saved = None
-        _mark_touched(model, {n: g for i, (n, g) in enumerate((n, grads.get(n)) for n in model._ae_param_names)
-                              if ctx.needs_input_grad[2 + i]})
+        mark_touched(model, {n: grads.get(n) for i, n in enumerate(model._ae_param_names) if ctx.needs_input_grad[2 + i]})
         return (None, None) + tuple(grads.get(n) if ctx.needs_input_grad[2 + i] else None
                                     for i, n in enumerate(model._ae_param_names))
 
@@ -317,105 +320,103 @@ class AV_Fusion_Model_Frames(nn.Module):
         has_bn = self._dec_plan[j][5]
         return self.stft_decoder[idx], (self.stft_decoder[idx + 1] if has_bn else None)
 
-    @staticmethod
-    def _pad_c(t, dim, c):
-        """zero-pad dimension `dim` of t to c entries (BatchNorm kernels take C = power of two >= 4: a 2-channel layer
-        runs with two dead channels, which stay exactly zero through BN (beta 0), tanh and the backward pass)."""
-        if t.shape[dim] == c:
-            return t.contiguous()
-        shp = list(t.shape)
-        shp[dim] = c - t.shape[dim]
-        return torch.cat((t, torch.zeros(shp, device=t.device, dtype=t.dtype)), dim=dim).contiguous()
-
-    def _bn2d_stats(self, y, bn, c_real, count, train):
-        """(mean, invstd) of a channels-last map whose last c - c_real channels are zero padding."""
-        c = y.shape[-1]
-        if c == c_real:
-            rm, rv = bn.running_mean, bn.running_var
-        else:
-            rm = self._pad_c(bn.running_mean, 0, c)
-            rv = torch.cat((bn.running_var, torch.ones(c - c_real, device=y.device, dtype=torch.float32)))
-        if not train:
-            return ops.bn_eval_stats(rm, rv, bn.eps)
-        mean, invstd = ops.bn_finalize(ops.bn_stats(y, c), count, rm, rv, bn.num_batches_tracked, bn.eps, bn.momentum)
-        if c != c_real:
-            bn.running_mean.copy_(rm[:c_real])
-            bn.running_var.copy_(rv[:c_real])
-        return mean, invstd
-
-    def _ae_forward(self, x_a, train=True):
+    def _stft_encoder_fwd(self, x_a, train, seq_out=None, bn_sync=None):
+        """K10: conv -> BatchNorm -> tanh per layer on x_a [B,2,T_a,F] (NCHW).  `seq_out` = (flat buffer, strides) makes the last
+        layer's BN + tanh write there (the LSTM sequence buffer).  -> (last activation NHWC, or None with seq_out; saved)."""
         b = x_a.shape[0]
-        assert tuple(x_a.shape[1:]) == (2, self.t_a, self.n_bins)
-        x_a = x_a.contiguous().float()
-        sv = {"enc": [], "dec": []}
-        cur, nchw = x_a, True
+        saved, cur, nchw = [], x_a, True
         for i, (ci, co, st, pw) in enumerate(self._enc_plan):
             conv, bn = self._aud(i)
             y = ops.conv2d_fwd(cur, conv.weight.detach(), st, pw, nchw)
             ho, wo = y.shape[1], y.shape[2]
-            mean, invstd = self._bn2d_stats(y, bn, co, b * ho * wo, train)
+            if train:
+                mean, invstd = _bn_train_stats(ops.bn_stats(y, co), b * ho * wo, bn, bn_sync)
+            else:
+                mean, invstd = ops.bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
             y5 = y.view(b, 1, ho, wo, co)
-            out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, bn.weight.detach(), bn.bias.detach(), 1, ops.BN_TANH)
-            sv["enc"].append(dict(x=cur, nchw=nchw, y=y5, mean=mean, invstd=invstd, out=out, hw=(ho, wo)))
-            cur, nchw = out.view(b, ho, wo, co), False
+            buf, strides = seq_out if seq_out is not None and i == len(self._enc_plan) - 1 else (None, None)
+            out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, bn.weight.detach(), bn.bias.detach(), 1, ops.BN_TANH, out=buf, strides=strides)
+            saved.append(dict(x=cur, nchw=nchw, y=y5, mean=mean, invstd=invstd, out=out, strides=strides, hw=(ho, wo)))
+            cur, nchw = out.view(b, ho, wo, co) if strides is None else None, False
+        return cur, saved
+
+    def _stft_encoder_bwd(self, saved, dout, out, strides, bn_reduce, need, gbuf, out_grads):
+        """Backward of _stft_encoder_fwd.  dout / out / strides: gradient and value of the last layer's activation as
+        ops.bn_pool_act_bwd takes them (strided when they live in the LSTM sequence buffer).  `need[name]` says which
+        parameter gradients are wanted, `gbuf(name)` -> (buffer, beta) gives where they go; results are entered in out_grads."""
+        b = saved[0]["x"].shape[0]
+        for i in reversed(range(len(self._enc_plan))):
+            ci, co, st, pw = self._enc_plan[i]
+            conv, bn = self._aud(i)
+            s = saved[i]
+            ho, wo = s["hw"]
+            gw, gb, acc = _bn_grad_bufs("stft_encoder", 3 * i + 1, need, gbuf, out_grads)
+            dy = ops.bn_pool_act_bwd(dout, out, None, s["y"], s["mean"], s["invstd"], bn.weight.detach(), 1, ops.BN_TANH,
+                                     strides=strides, dgamma=gw, dbeta=gb, accumulate=acc, reduce_fn=bn_reduce).view(b, ho, wo, co)
+            wname = f"stft_encoder.{3 * i}.weight"
+            if need.get(wname, False):
+                buf, beta = gbuf(wname)
+                ops.conv2d_wgrad(s["x"], dy, conv.weight.shape, st, pw, s["nchw"], dw=buf, beta=beta)
+                out_grads[wname] = buf
+            if i > 0:
+                below = saved[i - 1]
+                dcur = ops.conv2d_dgrad(dy, conv.weight.detach(), below["hw"], st, pw)
+                dout, out, strides = dcur.view(below["y"].shape), below["out"], None
+
+    def _ae_forward(self, x_a, train=True):
+        b = x_a.shape[0]
+        assert tuple(x_a.shape[1:]) == (2, self.t_a, self.n_bins)
+        code, enc = self._stft_encoder_fwd(x_a.contiguous().float(), train)      # per-rank BatchNorm statistics whatever set_bn_sync says
+        sv = {"enc": enc, "dec": []}
+        cur = ops.Map(code)
         for j, (ci, co, k, st, op, has_bn) in enumerate(self._dec_plan):
             convt, bn = self._dec(j)
-            ci_p = cur.shape[-1]
-            co_p = max(co, 4) if has_bn else co
-            w = self._pad_c(self._pad_c(convt.weight.detach(), 0, ci_p), 1, co_p)
-            y = ops.convt2d_fwd(cur, w, st, op, out_nhwc=has_bn)
-            rec = dict(x=cur, w=w, hw_in=(cur.shape[1], cur.shape[2]))
+            ho, wo = ops.convt2d_out(cur.h, cur.w, k[1], st, op)
+            if has_bn:      # channels-last, padded to what the BatchNorm kernels take: the dead channels must be (and stay) exactly zero
+                cp = cpad(co)
+                y = (torch.zeros if cp != co else torch.empty)(b, ho, wo, cp, device=x_a.device, dtype=torch.float32)
+                ymap = ops.Map(y, c=co)
+            else:           # the last layer writes the network's NCHW output
+                ymap = ops.Map(torch.empty(b, co, ho, wo, device=x_a.device, dtype=torch.float32), nchw=True)
+            ops.conv_gen_big(cur, convt.weight.detach(), None, ymap, st, ops.CONVT_PAD)
+            rec = dict(x=cur, y=ymap)
             if has_bn:
-                ho, wo = y.shape[1], y.shape[2]
-                mean, invstd = self._bn2d_stats(y, bn, co, b * ho * wo, train)
-                gamma, beta = self._pad_c(bn.weight.detach(), 0, co_p), self._pad_c(bn.bias.detach(), 0, co_p)
-                y5 = y.view(b, 1, ho, wo, co_p)
-                out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, gamma, beta, 1, ops.BN_TANH)
-                rec.update(y=y5, mean=mean, invstd=invstd, gamma=gamma, out=out, hw=(ho, wo))
-                cur = out.view(b, ho, wo, co_p)
+                mean, invstd = bn_stats_padded(y, bn, co, b * ho * wo, train)
+                gamma = pad_c(bn.weight.detach(), cp)
+                y5 = y.view(b, 1, ho, wo, cp)
+                out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, gamma, pad_c(bn.bias.detach(), cp), 1, ops.BN_TANH)
+                rec.update(y5=y5, mean=mean, invstd=invstd, gamma=gamma, out=out)
+                cur = ops.Map(out.view(b, ho, wo, cp), c=co)
             else:
-                cur = y
+                cur = ymap
             sv["dec"].append(rec)
-        return cur, sv
+        return cur.t, sv
 
     def _ae_backward(self, sv, d_out, bn_eval=False):
         grads = {}
-        bn_reduce = _bn_eval_reduce if bn_eval else None
-        b = d_out.shape[0]
+        bn_reduce = bn_eval_reduce if bn_eval else None
         dcur = d_out                                    # NCHW gradient of the last (BN-less) layer's output
         for j in reversed(range(len(self._dec_plan))):
             ci, co, k, st, op, has_bn = self._dec_plan[j]
             s = sv["dec"][j]
-            idx = 3 * j
+            w = self._dec(j)[0].weight.detach()
             if has_bn:
-                ho, wo = s["hw"]
-                co_p = s["gamma"].shape[0]
-                gw = torch.empty(co_p, device=d_out.device, dtype=torch.float32)
-                gb = torch.empty(co_p, device=d_out.device, dtype=torch.float32)
-                dy = ops.bn_pool_act_bwd(dcur.view(b, 1, ho, wo, co_p), s["out"], None, s["y"], s["mean"], s["invstd"], s["gamma"], 1,
-                                         ops.BN_TANH, dgamma=gw, dbeta=gb, reduce_fn=bn_reduce).view(b, ho, wo, co_p)
-                grads[f"stft_decoder.{idx + 1}.weight"] = gw[:co].clone()
-                grads[f"stft_decoder.{idx + 1}.bias"] = gb[:co].clone()
+                y5 = s["y5"]
+                gw, gb = torch.empty_like(s["gamma"]), torch.empty_like(s["gamma"])
+                dy = ops.bn_pool_act_bwd(dcur.view(y5.shape), s["out"], None, y5, s["mean"], s["invstd"], s["gamma"], 1,
+                                         ops.BN_TANH, dgamma=gw, dbeta=gb, reduce_fn=bn_reduce)
+                grads[f"stft_decoder.{3 * j + 1}.weight"] = gw[:co].clone()
+                grads[f"stft_decoder.{3 * j + 1}.bias"] = gb[:co].clone()
+                dymap = ops.Map(dy.view(s["y"].t.shape), c=co)
             else:
-                dy = dcur
-            dw = ops.convt2d_wgrad(s["x"], dy, s["w"].shape, st, op, out_nhwc=has_bn)
-            grads[f"stft_decoder.{idx}.weight"] = dw[:ci, :co].contiguous()
-            dcur = ops.convt2d_dgrad(dy, s["w"], s["hw_in"], st, op, out_nhwc=has_bn)
-        n_layers = len(self._enc_plan)
-        for i in reversed(range(n_layers)):
-            ci, co, st, pw = self._enc_plan[i]
-            conv, bn = self._aud(i)
-            s = sv["enc"][i]
-            ho, wo = s["hw"]
-            gw = torch.empty(co, device=d_out.device, dtype=torch.float32)
-            gb = torch.empty(co, device=d_out.device, dtype=torch.float32)
-            dy = ops.bn_pool_act_bwd(dcur.view(b, 1, ho, wo, co), s["out"], None, s["y"], s["mean"], s["invstd"], bn.weight.detach(), 1,
-                                     ops.BN_TANH, dgamma=gw, dbeta=gb, reduce_fn=bn_reduce).view(b, ho, wo, co)
-            grads[f"stft_encoder.{3 * i + 1}.weight"], grads[f"stft_encoder.{3 * i + 1}.bias"] = gw, gb
-            grads[f"stft_encoder.{3 * i}.weight"] = ops.conv2d_wgrad(s["x"], dy, conv.weight.shape, st, pw, s["nchw"])
-            if i > 0:
-                hin, win = sv["enc"][i - 1]["hw"]
-                dcur = ops.conv2d_dgrad(dy, conv.weight.detach(), (hin, win), st, pw)
+                dymap = ops.Map(dcur, nchw=True)
+            grads[f"stft_decoder.{3 * j}.weight"] = ops.conv_gen_wgrad(s["x"], dymap, w.shape, st, ops.CONVT_PAD)
+            xm = s["x"]
+            dcur = (torch.zeros_like if xm.c != xm.c_alloc else torch.empty_like)(xm.t)
+            ops.conv_gen_small(dymap, w, None, ops.Map(dcur, c=xm.c), st, ops.CONVT_PAD)
+        last = sv["enc"][-1]
+        self._stft_encoder_bwd(sv["enc"], dcur.view(last["y"].shape), last["out"], None, bn_reduce, dict.fromkeys(self._ae_param_names, True),
+                               lambda name: (torch.empty_like(self.get_parameter(name)), 0), grads)      # all needed, fresh buffers
         return grads
 
     def _fusion_fwd(self, seq, sv):
@@ -425,12 +426,7 @@ class AV_Fusion_Model_Frames(nn.Module):
         time there and costs accuracy; `precise` only switches the conv3d MFMAs."""
         pr = ops.MODE_F32
         b, l = seq.shape[0], self.latent_channels
-        seq2d = seq.view(b * l, seq.shape[2])
-        gx = torch.empty(b * l, 2048, device=seq.device, dtype=torch.float32)
-        ops.gemm(seq2d, self.lstm.weight_ih_l0.detach(), out=gx[:, :1024], precise=pr, split_k=1)
-        ops.gemm(seq2d, self.lstm.weight_ih_l0_reverse.detach(), out=gx[:, 1024:], precise=pr, split_k=1)
-        av, hp, gs, cs = ops.lstm_fwd(gx.view(b, l, 2, 4, 256), self.lstm.weight_hh_l0.detach(),
-                                      self.lstm.weight_hh_l0_reverse.detach())
+        av, hp, gs, cs = bilstm_fwd(seq, self.lstm)
         h1 = ops.gemm(av.view(b, l * 512), self.fc1.weight.detach(), act=ops.ACT_TANH, precise=pr)
         fused = ops.gemm(h1, self.fc2.weight.detach(), act=ops.ACT_TANH, precise=pr)
         sv.update(seq=seq, av=av, hp=hp, gs=gs, cs=cs, h1=h1, fused=fused)
@@ -438,7 +434,7 @@ class AV_Fusion_Model_Frames(nn.Module):
 
     def _fusion_bwd(self, sv, dfused, wgrad_gemm):
         """Backward of _fusion_fwd: parameter gradients through `wgrad_gemm(name, dz, x)`; returns the gate gradient dgx
-        [B*16, 2048], from which _fusion_dseq forms d(seq) -- kept apart so that the gradient all-reduce of the
+        [B*16, 2048], from which bilstm_dseq forms d(seq) -- kept apart so that the gradient all-reduce of the
         fusion weights can start in between."""
         pr = ops.MODE_F32
         seq, fused, h1, av = sv["seq"], sv["fused"], sv["h1"], sv["av"]
@@ -451,31 +447,15 @@ class AV_Fusion_Model_Frames(nn.Module):
         dav = ops.gemm(dz1, self.fc1.weight.detach(), trans_b=True, precise=pr)
         dgx = ops.lstm_bwd(dav.view(b, l, 512), self.lstm.weight_hh_l0.detach(), self.lstm.weight_hh_l0_reverse.detach(),
                            sv["gs"], sv["cs"]).view(b * l, 2048)
-        seq2d = seq.view(b * l, seq.shape[2])
-        hp2 = sv["hp"].view(b * l, 512)
-        wgrad_gemm("lstm.weight_ih_l0", dgx[:, :1024], seq2d)
-        wgrad_gemm("lstm.weight_ih_l0_reverse", dgx[:, 1024:], seq2d)
-        wgrad_gemm("lstm.weight_hh_l0", dgx[:, :1024], hp2[:, :256])
-        wgrad_gemm("lstm.weight_hh_l0_reverse", dgx[:, 1024:], hp2[:, 256:])
+        for name, dz, x in bilstm_wgrad_operands(dgx, seq, sv["hp"]):
+            wgrad_gemm(name, dz, x)
         return dgx
-
-    def _fusion_dseq(self, dgx, b):
-        pr = ops.MODE_F32
-        dseq = ops.gemm(dgx[:, :1024], self.lstm.weight_ih_l0.detach(), trans_b=True, precise=pr)
-        ops.gemm(dgx[:, 1024:], self.lstm.weight_ih_l0_reverse.detach(), trans_b=True, out=dseq, beta=1, precise=pr)
-        return dseq.view(b, self.latent_channels, -1)
 
     def set_bn_sync(self, reduce_fn):
         """Global-batch BatchNorm for data-parallel training (EXTENSION; the reference is single-device, where BatchNorm
         sees the whole batch, avse_model_final.py:35,...,103): `reduce_fn(t)` must sum the float64 tensor t in place over
         the data-parallel ranks (trainer.TrainStep(sync_bn=True) installs one); None restores per-rank statistics."""
         self._bn_sync = reduce_fn
-
-    def _bn_train_stats(self, part, count, bn):
-        if self._bn_sync is None:
-            return ops.bn_finalize(part, count, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum)
-        return ops.bn_finalize_synced(part, count, self._bn_sync, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                      bn.eps, bn.momentum)
 
     def _engine_forward(self, x_a, x_v, train=True):
         # train=False (model.eval()): BatchNorm uses its running statistics and leaves them untouched (forward only)
@@ -487,7 +467,7 @@ class AV_Fusion_Model_Frames(nn.Module):
         dev = x_v.device
         ts = t * self.s_v
         seq = torch.empty(b, self.latent_channels, 2 * ts, device=dev, dtype=torch.float32)
-        sv = {"x_v": x_v, "x_a": x_a, "seq": seq, "vis": [], "aud": []}
+        sv = {"x_v": x_v, "x_a": x_a, "seq": seq, "vis": []}
         # --- visual encoder (K7-K9).  16-bit path: every pooled activation is also written as IEEE half by its producer
         # (the rounding the next conv's MFMA staging would apply, done once), so that conv reads half the bytes and copies;
         # the f32 tensor stays for the backward pass (weight gradient operand, BatchNorm / LeakyReLU backward).
@@ -513,7 +493,7 @@ class AV_Fusion_Model_Frames(nn.Module):
                 y, part = ops.conv3d_igemm(act_in if act_in16 is None else act_in16, wt, co, pad, pr, want_stats=train)
             hh, ww = y.shape[2], y.shape[3]
             if train:
-                mean, invstd = self._bn_train_stats(part, b * t * hh * ww, bn)
+                mean, invstd = _bn_train_stats(part, b * t * hh * ww, bn, self._bn_sync)
             else:
                 mean, invstd = ops.bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
             x_b = act_inb
@@ -540,29 +520,9 @@ class AV_Fusion_Model_Frames(nn.Module):
             sv["vis"].append(dict(x=act_in, x_bf16=x_b, y=y, mean=mean, invstd=invstd, out=out, arg=arg, strides=strides, recompute=recompute))
             act_in = out
         # --- STFT encoder (K10)
-        cur, nchw = x_a, True
-        n_layers = len(self._enc_plan)
         seq_aud = seq.view(-1)[ts:]
         aud_strides = (self.latent_channels * 2 * ts, 0, 1, 2 * ts)
-        for i, (ci, co, st, pw) in enumerate(self._enc_plan):
-            conv, bn = self._aud(i)
-            y = ops.conv2d_fwd(cur, conv.weight.detach(), st, pw, nchw)
-            ho, wo = y.shape[1], y.shape[2]
-            if train:
-                mean, invstd = self._bn_train_stats(ops.bn_stats(y, co), b * ho * wo, bn)
-            else:
-                mean, invstd = ops.bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
-            y5 = y.view(b, 1, ho, wo, co)
-            last = i == n_layers - 1
-            if last and self._enc_pool is None:
-                out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, bn.weight.detach(), bn.bias.detach(), 1, ops.BN_TANH,
-                                             out=seq_aud, strides=aud_strides)
-                strides = aud_strides
-            else:
-                out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, bn.weight.detach(), bn.bias.detach(), 1, ops.BN_TANH)
-                strides = None
-            sv["aud"].append(dict(x=cur, nchw=nchw, y=y5, mean=mean, invstd=invstd, out=out, strides=strides, hw=(ho, wo)))
-            cur, nchw = out.view(b, ho, wo, co) if strides is None else None, False
+        cur, sv["aud"] = self._stft_encoder_fwd(x_a, train, None if self._enc_pool is not None else (seq_aud, aud_strides), self._bn_sync)
         if self._enc_pool is not None:
             ho, wo = sv["aud"][-1]["hw"]
             _lib.call("maavss_adaptive_pool_fwd", cur.data_ptr(), seq_aud.data_ptr(), b, ho, wo, self.latent_channels,
@@ -587,7 +547,7 @@ class AV_Fusion_Model_Frames(nn.Module):
         all-reduce starts while fc2 / fc1 / the LSTM are still in their backward pass)."""
         # conv backward operands: bf16 (gradients need the exponent range), or exact f32; Linear layers always f32
         pr_conv, pr = (ops.MODE_F32 if self.precise_bwd else ops.MODE_BF16), ops.MODE_F32
-        bn_reduce = _bn_eval_reduce if bn_eval else self._bn_sync       # `bn_eval`: the forward used running statistics
+        bn_reduce = bn_eval_reduce if bn_eval else self._bn_sync       # `bn_eval`: the forward used running statistics
         out_grads = {}
         pd = dict(self.named_parameters())
 
@@ -634,47 +594,18 @@ class AV_Fusion_Model_Frames(nn.Module):
                        if n.startswith("visual_encoder.") or n.startswith("stft_encoder."))
         if not enc_need:
             return out_grads
-        dseq = self._fusion_dseq(dgx, b)
-
-        def bn_grads(prefix, idx):
-            nw, nb = f"{prefix}.{idx}.weight", f"{prefix}.{idx}.bias"
-            if not (need.get(nw, False) or need.get(nb, False)):
-                return None, None, False
-            gw, beta = gbuf(nw)
-            gb, _ = gbuf(nb)
-            out_grads[nw], out_grads[nb] = gw, gb
-            return gw, gb, bool(beta)
+        dseq = bilstm_dseq(dgx, self.lstm).view(b, l, -1)
 
         # --- STFT encoder backward
-        dcur = None
-        n_layers = len(self._enc_plan)
-        seq_aud_grad = dseq.view(-1)[ts:]
-        for i in reversed(range(n_layers)):
-            ci, co, st, pw = self._enc_plan[i]
-            conv, bn = self._aud(i)
-            s = sv["aud"][i]
-            ho, wo = s["hw"]
-            if i == n_layers - 1:
-                if self._enc_pool is not None:
-                    dcur = torch.empty(b, ho, wo, co, device=dseq.device, dtype=torch.float32)
-                    _lib.call("maavss_adaptive_pool_bwd", seq_aud_grad.data_ptr(), dcur.data_ptr(), b, ho, wo, co,
-                              self._enc_pool[0], self._enc_pool[1], l * 2 * ts, 1, 2 * ts, _lib.stream_ptr())
-                    dout, out, strides = dcur.view(b, 1, ho, wo, co), s["out"], None
-                else:
-                    dout, out, strides = seq_aud_grad, sv["seq"].view(-1)[ts:], s["strides"]
-            else:
-                dout, out, strides = dcur.view(b, 1, ho, wo, co), s["out"], None
-            gw, gb, acc = bn_grads("stft_encoder", 3 * i + 1)
-            dy = ops.bn_pool_act_bwd(dout, out, None, s["y"], s["mean"], s["invstd"], bn.weight.detach(), 1, ops.BN_TANH,
-                                     strides=strides, dgamma=gw, dbeta=gb, accumulate=acc, reduce_fn=bn_reduce).view(b, ho, wo, co)
-            wname = f"stft_encoder.{3 * i}.weight"
-            if need.get(wname, False):
-                buf, beta = gbuf(wname)
-                ops.conv2d_wgrad(s["x"], dy, conv.weight.shape, st, pw, s["nchw"], dw=buf, beta=beta)
-                out_grads[wname] = buf
-            if i > 0:
-                hin, win = sv["aud"][i - 1]["hw"]
-                dcur = ops.conv2d_dgrad(dy, conv.weight.detach(), (hin, win), st, pw)
+        last = sv["aud"][-1]
+        if self._enc_pool is not None:
+            dcur = torch.empty(last["y"].shape, device=dseq.device, dtype=torch.float32)
+            _lib.call("maavss_adaptive_pool_bwd", dseq.view(-1)[ts:].data_ptr(), dcur.data_ptr(), b, *last["hw"], l,
+                      self._enc_pool[0], self._enc_pool[1], l * 2 * ts, 1, 2 * ts, _lib.stream_ptr())
+            dout, out = dcur, last["out"]
+        else:
+            dout, out = dseq.view(-1)[ts:], sv["seq"].view(-1)[ts:]
+        self._stft_encoder_bwd(sv["aud"], dout, out, last["strides"], bn_reduce, need, gbuf, out_grads)
         # --- visual encoder backward
         dcur = None
         for i in reversed(range(5)):
@@ -685,7 +616,7 @@ class AV_Fusion_Model_Frames(nn.Module):
                 dout, out = dseq, sv["seq"]
             else:
                 dout, out = dcur, s["out"]
-            gw, gb, acc = bn_grads("visual_encoder", 4 * i + 1)
+            gw, gb, acc = _bn_grad_bufs("visual_encoder", 4 * i + 1, need, gbuf, out_grads)
             wname = f"visual_encoder.{4 * i}.weight"
             if i == 0:
                 # first layer: the network input needs no gradient, so dy has one consumer, the weight gradient -- which

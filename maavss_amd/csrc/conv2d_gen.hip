@@ -1,12 +1,16 @@
-// K19: the biased 2-D convolutions of the phasegram variant avse_model.AV_Fusion_Model
-// (avse_model.py:410-711) -- Conv2d / ConvTranspose2d with kernels (1,9) [phasegram encoder / decoder, :433,452] and
-// (5,5) [STFT encoder / decoder, :494,591], strides in {1,2}^2, any padding, bias.
-// One formulation serves all six operators.  A "small" map S [B][Hs][Ws][Cs] and a "big" map G [B][Hb][Wb][Cb] are
+// K19: every 2-D convolution that is not the STFT encoder's own conv2d.hip.  It serves
+//   * the biased layers of the phasegram variant avse_model.AV_Fusion_Model (avse_model.py:410-711):
+//     Conv2d / ConvTranspose2d with kernels (1,9) [phasegram encoder / decoder, :433,452] and (5,5) [STFT encoder / decoder,
+//     :494,591], strides in {1,2}^2, bias;
+//   * the bias-free STFT decoder of AV_Fusion_Model_Frames (formerly K11; avse_model_final.py:155-193, audio_ae_forward
+//     :254-256): ConvTranspose2d with kernels (3,9) / (3,10), padding (1,4), strides in {1,2}^2, output_padding = stride - 1
+//     -- (3,10) = 30 taps is what CG_MAX_TAPS is sized for.
+// One formulation serves all of them.  A "small" map S [B][Hs][Ws][Cs] and a "big" map G [B][Hb][Wb][Cb] are
 // tied by  by = sy*sh - ph + kh,  bx = sx*sw - pw + kw  and a weight w[cs][cb][kh][kw]:
 //   gather_small:  S = bias + sum_{cb,kh,kw} G * w      = Conv2d forward (w = [Co][Ci])   = ConvTranspose2d input gradient
 //   gather_big:    G = bias + sum_{cs,kh,kw} S * w      = ConvTranspose2d forward (w = [Ci][Co]) = Conv2d input gradient
 //   wgrad:         dw[cs][cb][kh][kw] = sum_{b,sy,sx} S * G                                  (both operators)
-// -- the PyTorch weight layouts of Conv2d ([Co][Ci]) and ConvTranspose2d ([Ci][Co]) are both [small][big].
+// -- the PyTorch weight layouts of Conv2d ([Co][Ci]) and ConvTranspose2d ([Ci][Co]) are both [small][big]; bias may be null.
 // Tensors are addressed through explicit element strides (b, y, x, c), so the network's NCHW inputs / outputs and the
 // channels-last activations (optionally channel-padded for the BatchNorm kernels) need no copies.
 // A few MFLOP per clip: direct kernels, one thread per output element; latency / HBM-bound like conv2d.hip.
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(256) void cgen_big_kernel(const float* __restrict__
 }
 
 // one block per (cs, cb) pair and chunk of small-map positions; partials[chunk][cs][cb][kh*kw]
-#define CG_MAX_TAPS 25
+#define CG_MAX_TAPS 30
 __global__ __launch_bounds__(256) void cgen_wgrad_kernel(const float* __restrict__ S, const float* __restrict__ G,
                                                          float* __restrict__ partials, CGen g, int64_t pos_per_chunk) {
   __shared__ float red[4][CG_MAX_TAPS];

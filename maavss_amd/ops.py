@@ -4,6 +4,8 @@ Tensors are torch CUDA tensors used purely as device-memory handles: every funct
 device pointers + explicit sizes + the current HIP stream to libmaavss_hip.so.  No torch math here.
 Layouts: visual activations channels-last [B,T,H,W,C]; STFT-encoder activations NHWC.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -359,49 +361,7 @@ def conv2d_wgrad(x, dy, w_shape, stride, pw, in_nchw, dw=None, beta=0):
     return dw
 
 
-# ---------------------------------------------------------------------------------------------- convt2d (STFT decoder)
-def convt2d_out(h, w, kw, stride, opad):
-    return (h - 1) * stride[0] + 1 + opad[0], (w - 1) * stride[1] - 8 + kw + opad[1]
-
-
-def convt2d_fwd(x, w, stride, opad, out_nhwc):
-    """x NHWC [B,Hi,Wi,Ci], w [Ci,Co,3,kw] -> y NHWC [B,Ho,Wo,Co] or NCHW [B,Co,Ho,Wo] (last decoder layer)."""
-    _f32(x, w)
-    b, hi, wi, ci = x.shape
-    assert w.shape[0] == ci and w.shape[2] == 3
-    co, kw = w.shape[1], w.shape[3]
-    ho, wo = convt2d_out(hi, wi, kw, stride, opad)
-    y = torch.empty((b, ho, wo, co) if out_nhwc else (b, co, ho, wo), device=x.device, dtype=torch.float32)
-    call("maavss_convt2d_fwd", ptr(x), ptr(w), ptr(y), b, ci, hi, wi, co, kw, stride[0], stride[1], opad[0], opad[1],
-         1 if out_nhwc else 0, stream_ptr())
-    return y
-
-
-def convt2d_dgrad(dy, w, in_hw, stride, opad, out_nhwc):
-    _f32(dy, w)
-    ci, co, kw = w.shape[0], w.shape[1], w.shape[3]
-    b = dy.shape[0]
-    dx = torch.empty(b, in_hw[0], in_hw[1], ci, device=dy.device, dtype=torch.float32)
-    call("maavss_convt2d_dgrad", ptr(dy), ptr(w), ptr(dx), b, ci, in_hw[0], in_hw[1], co, kw, stride[0], stride[1], opad[0],
-         opad[1], 1 if out_nhwc else 0, stream_ptr())
-    return dx
-
-
-def convt2d_wgrad(x, dy, w_shape, stride, opad, out_nhwc):
-    _f32(x, dy)
-    b, hi, wi, ci = x.shape
-    co, kw = w_shape[1], w_shape[3]
-    nchunk = query("maavss_convt2d_wgrad_nchunk", b, hi, wi)
-    ws = torch.empty(nchunk * ci * co * 3 * kw, device=x.device, dtype=torch.float32)
-    dw = torch.empty(ci, co, 3, kw, device=x.device, dtype=torch.float32)
-    call("maavss_convt2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws), b, ci, hi, wi, co, kw, stride[0], stride[1], opad[0],
-         opad[1], 1 if out_nhwc else 0, 0, stream_ptr())
-    return dw
-
-
 # ---------------------------------------------------------------------------------------------- generic conv2d (K19)
-import ctypes as _ct
-
 ACT_LEAKY = 3
 
 
@@ -419,7 +379,7 @@ class Map:
             self.b, self.h, self.w, self.c_alloc = t.shape
             st = (t.stride(0), t.stride(1), t.stride(2), t.stride(3))
         self.c = self.c_alloc if c is None else c
-        self.strides = (_ct.c_int64 * 4)(*st)
+        self.strides = (ctypes.c_int64 * 4)(*st)
 
 
 def _cgen_args(small, big, w, stride, pad):
@@ -450,6 +410,35 @@ def conv_gen_wgrad(small, big, w_shape, stride, pad, dw=None, beta=0):
     call("maavss_conv2d_gen_wgrad", ptr(small.t), ptr(big.t), ptr(dw), ptr(ws), small.b, cs, small.h, small.w, cb, big.h, big.w, kh, kw,
          stride[0], stride[1], pad[0], pad[1], small.strides, big.strides, int(beta), stream_ptr())
     return dw
+
+
+# ConvTranspose2d(k=(3,kw), padding (1,4), bias=False) of the STFT decoder, on dense tensors: x / dx NHWC, y / dy NHWC or NCHW
+CONVT_PAD = (1, 4)
+
+
+def convt2d_out(h, w, kw, stride, opad):
+    return (h - 1) * stride[0] + 1 + opad[0], (w - 1) * stride[1] - 8 + kw + opad[1]
+
+
+def convt2d_fwd(x, w, stride, opad, out_nhwc):
+    """x NHWC [B,Hi,Wi,Ci], w [Ci,Co,3,kw] -> y NHWC [B,Ho,Wo,Co] or NCHW [B,Co,Ho,Wo] (last decoder layer)."""
+    b, hi, wi, ci = x.shape
+    assert w.shape[0] == ci and w.shape[2] == 3
+    co, kw = w.shape[1], w.shape[3]
+    ho, wo = convt2d_out(hi, wi, kw, stride, opad)
+    y = torch.empty((b, ho, wo, co) if out_nhwc else (b, co, ho, wo), device=x.device, dtype=torch.float32)
+    conv_gen_big(Map(x), w, None, Map(y, nchw=not out_nhwc), stride, CONVT_PAD)
+    return y
+
+
+def convt2d_dgrad(dy, w, in_hw, stride, opad, out_nhwc):
+    dx = torch.empty(dy.shape[0], in_hw[0], in_hw[1], w.shape[0], device=dy.device, dtype=torch.float32)
+    conv_gen_small(Map(dy, nchw=not out_nhwc), w, None, Map(dx), stride, CONVT_PAD)
+    return dx
+
+
+def convt2d_wgrad(x, dy, w_shape, stride, opad, out_nhwc):
+    return conv_gen_wgrad(Map(x), Map(dy, nchw=not out_nhwc), w_shape, stride, CONVT_PAD)
 
 
 def channel_sum(m, out=None, beta=0):

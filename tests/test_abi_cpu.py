@@ -18,7 +18,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(cdll, name), f"{name} declared in include/maavss.h but not exported"
     L = _lib.lib()
     assert L.cdll.maavss_arch() == b"gfx950"
-    assert L.cdll.maavss_version() == _lib.header_abi_version() == 400
+    assert L.cdll.maavss_version() == _lib.header_abi_version() == 401
 
 
 def test_no_cpu_fallback():
@@ -101,3 +101,19 @@ def test_round4_argument_checks():
         _lib.call("maavss_vit_qkv_mx", 256, 256, rows, 1152, 2, None)
     with pytest.raises(_lib.MaavssError, match="32-bit"):
         _lib.call("maavss_vit_ws_gemm_ln_mx", 256, (rows + 63) // 64 * 64, 256, 256, 256, 1e-6, 256, 256, 256, rows, 384, 1.0, 2, None)
+
+
+def test_generic_conv2d_refuses_more_than_30_taps_before_any_launch():
+    """csrc/conv2d_gen.hip keeps one accumulator per tap: 30 = the STFT decoder's (3,10) kernel is the limit of all three entry points."""
+    strides = (ctypes.c_int64 * 4)(1, 1, 1, 1)
+
+    def args(kh, kw, s_strides):      # B, Cs, Hs, Ws, Cb, Hb, Wb, kernel, stride 1, pad 0, strides
+        return (1, 1, 4, 4, 1, 3 + kh, 3 + kw, kh, kw, 1, 1, 0, 0, s_strides, strides)
+
+    for name, lead, tail in (("maavss_conv2d_gen_small", (256, 256, None, 256), (None,)), ("maavss_conv2d_gen_big", (256, 256, None, 256), (None,)),
+                             ("maavss_conv2d_gen_wgrad", (256, 256, 256, 256), (0, None))):
+        with pytest.raises(_lib.MaavssError, match="kernel 4x8 has more than 30 taps"):
+            _lib.call(name, *lead, *args(4, 8, strides), *tail)
+        # (5,6) = 30 taps passes that check and is stopped by the next one
+        with pytest.raises(_lib.MaavssError, match="stride arrays missing"):
+            _lib.call(name, *lead, *args(5, 6, None), *tail)

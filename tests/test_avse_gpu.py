@@ -286,7 +286,7 @@ def test_backward_through_an_eval_mode_forward(precise):
 
 @pytest.mark.parametrize("name", ["S", "P"])
 def test_audio_autoencoder_matches_reference_golden(golden_dir, name):
-    """audio_ae_forward through the HIP engine (conv2d / convt2d / BN kernels) vs the reference's own numbers:
+    """audio_ae_forward through the HIP engine (conv2d / conv2d_gen / BN kernels) vs the reference's own numbers:
     output, loss, every encoder and decoder gradient, BN running statistics (train_audio_net.py:107-109)."""
     from oracle import avse_ref_cpu as orc
     z = np.load(os.path.join(golden_dir, f"avse_ae_{name}.npz"), allow_pickle=False)
