@@ -9,6 +9,7 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --overfit --steps 300 --lr 1e-4 --log_every 20     # one fixed batch: the loss has to fall
     python examples/train_synthetic.py --raw_video 360x640 [--autocontrast]   # decoded uint8 clips through VideoTransform first
     python examples/train_synthetic.py --raw_audio [--compress_audio]         # 44.1 kHz stereo int16 clips through AudioTransform first
+    python examples/train_synthetic.py --mix 2 --mix_snr 0 10                 # mix-and-separate: every clip + 2 others of the batch at 0..10 dB
 """
 import argparse
 import os
@@ -40,6 +41,9 @@ def main():
     ap.add_argument("--raw_audio", action="store_true",
                     help="feed 44.1 kHz stereo int16 clips through the GPU audio transform (downmix + resampling to 16 kHz)")
     ap.add_argument("--compress_audio", action="store_true", help="with --raw_audio: the reference's --compress_audio (run_config.py)")
+    ap.add_argument("--mix", type=int, default=0, metavar="K",
+                    help="mix-and-separate: add K other clips of the batch (1..4) to every clip's input; each clip is its own set of sinusoids")
+    ap.add_argument("--mix_snr", type=float, nargs=2, default=(0.0, 10.0), metavar=("LO", "HI"), help="with --mix: signal-to-interferer range in dB")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
@@ -59,8 +63,9 @@ def main():
     if a.raw_audio:
         audio_transform = maavss_amd.AudioTransform(16000, compress_audio=a.compress_audio)
         raw_length = audio_transform.input_length(length, raw_sr)      # the fewest 44.1 kHz samples that give `length` at 16 kHz
+    mixer = maavss_amd.Mixer(stft, a.mix, tuple(a.mix_snr)) if a.mix else None
     pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform, audio_transform=audio_transform,
-                                   audio_length=length if a.raw_audio else None)
+                                   audio_length=length if a.raw_audio else None, mixer=mixer)
 
     g = torch.Generator().manual_seed(0)
 
@@ -69,7 +74,18 @@ def main():
             frames = torch.randint(0, 256, (b, t_total, h0, w0, 3), generator=g, dtype=torch.uint8)
         else:
             frames = torch.rand(b * t_total, 3, w, w, generator=g)
-        if audio_transform is not None:
+        if mixer is not None:
+            # "instruments": every clip its own three partials (a random fundamental in 110..880 Hz, harmonics 1-3) over a little noise,
+            # so that the clips the mixer adds are other sources, not more of the same noise
+            n, sr = (raw_length, raw_sr) if audio_transform is not None else (length, 16000)
+            f0 = 110.0 * 2.0 ** (3.0 * torch.rand(b, 1, generator=g))
+            t = torch.arange(n, dtype=torch.float32)[None, :] / sr
+            audio = 0.02 * torch.randn(b, n, generator=g)
+            for h in (1, 2, 3):
+                audio = audio + (0.3 / h) * torch.sin(2 * torch.pi * h * f0 * t + 2 * torch.pi * torch.rand(b, 1, generator=g))
+            if audio_transform is not None:
+                audio = (32767 * audio[:, None, :].expand(b, 2, n)).to(torch.int16)
+        elif audio_transform is not None:
             audio = (0.3 * 32767 * torch.randn(b, 2, raw_length, generator=g)).clamp(-32768, 32767).to(torch.int16)
         else:
             audio = (0.3 * torch.randn(b, length, generator=g)).clamp(-1, 1)

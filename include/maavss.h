@@ -63,6 +63,37 @@ int maavss_stft_normalise(float* y, float* x, const float* noise, const float* c
 int maavss_istft(const float* spec, int64_t batch, int n_frames, int n_bins_in, const float* window, int n_fft, int hop,
                  int normalized, float* frames_ws, float* audio, int64_t audio_stride, void* stream);
 
+/* ---- EXTENSION: mix-and-separate training examples (maavss_amd.Mixer) --------------------------------------------------
+ * extends add_noise / gen_stft_example (av_dataset.py:217-220, 335-342), whose only corruption of the input is white noise on
+ * the STFT coefficients: the input becomes the clip plus other clips' audio at a chosen signal-to-interferer ratio, the target
+ * stays the clip's own STFT.  Added without a version bump (nothing existing changed meaning).
+ *   audio [batch][audio_stride], pool [n_pool][pool_stride] (length valid samples per row; pool may be audio itself);
+ *   partners [batch][k_slots] int32 on the DEVICE, 1 <= k_slots <= 4, entries in [0, n_pool) or -1 = empty slot (anything else is
+ *   read as empty: the values live on the device, the caller checks them);
+ *   s_b[n] = sum_k pool[partners[b][k]][n], f32, summed in slot order;
+ *   g_b = snr_factor[b] * sqrt(sum_n audio_b[n]^2 / sum_n s_b[n]^2), snr_factor[b] = 10^(-snr_db_b / 20) evaluated by the host
+ *   (the two mean powers' 1/length cancels); g_b = 0 exactly when clip b has no partner or either sum is 0, and also when the
+ *   quotient or the product is past float's range (an interferer some 1e-19 of the clip's level): no inf or NaN reaches an output.
+ * maavss_mix_gains writes gain [batch].  One workgroup per clip, sequential runs then a tree, no atomics: the bits of g_b depend on
+ * the clip, its partners and length only -- not on the launch or the run. */
+int maavss_mix_gains(const float* audio, int64_t batch, int64_t length, int64_t audio_stride, const float* pool, int64_t n_pool,
+                     int64_t pool_stride, const int* partners, int k_slots, const float* snr_factor, float* gain, void* stream);
+/* mixture [batch][mixture_stride] = audio_b + g_b * s_b (the waveform behind x: for listening, or as Enhancer input).  mixture must
+ * not overlap audio or pool (refused): other workgroups still read the rows one workgroup writes. */
+int maavss_mix_wave(const float* audio, int64_t batch, int64_t length, int64_t audio_stride, const float* pool, int64_t n_pool,
+                    int64_t pool_stride, const int* partners, int k_slots, const float* gain, float* mixture, int64_t mixture_stride,
+                    void* stream);
+/* x = y + (g_b * c_b) * STFT(s_b) + sigma * noise, with window / n_fft / hop / n_frames / n_bins_out / noise / seed as in
+ * maavss_stft_fwd and y [batch][2][n_frames][n_bins_out] READ: the output of maavss_stft_fwd(audio, x = NULL), after
+ * maavss_stft_normalise(x = NULL) when the clips are normalised -- the target is the plain call's, bit for bit.
+ * clip_absmax NULL: c_b = 1 and the in-kernel noise (noise = NULL) is maavss_stft_fwd's, element for element, for the same seed;
+ * clip_absmax [batch] (what maavss_stft_fwd wrote): c_b = 1 / (clip_absmax[b] + 1e-7) and the noise is maavss_stft_normalise's.
+ * x must not overlap y, noise or pool (refused); for a clip whose g_b * c_b is 0 or not finite
+ * x = y + sigma * noise.  Frames are paired inside a clip, so clip b's x depends on the launch through y alone. */
+int maavss_stft_mix_fwd(const float* pool, int64_t n_pool, int64_t length, int64_t pool_stride, const int* partners, int k_slots,
+                        int64_t batch, const float* window, int n_fft, int hop, int n_frames, int n_bins_out, const float* y, float* x,
+                        const float* noise, float sigma, uint64_t seed, const float* gain, const float* clip_absmax, void* stream);
+
 /* ---- generic f32 GEMM on MFMA -----------------------------------------------------------------
  * C[M,N] = act(alpha * op(A)[M,K] . op(B)[N,K]^T) (+ C when beta = 1).  Replaces the nn.Linear forwards
  * of avse_model_final.py:141-146,203-213,244-249,264-268, the LSTM input projection (:132,242) and the

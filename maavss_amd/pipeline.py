@@ -13,13 +13,15 @@ With `transform` (a VideoTransform) the pipeline starts one stage earlier, at th
 av_dataset.py:315-319 runs on the side stream in front of the extractor, into a per-slot frame buffer.  With `audio_transform` (an
 AudioTransform) and `audio_length` (the samples per clip the STFT is to see) the audio side does the same: the demuxer's PCM clips
 at their own rate go through av_dataset.py:203-215 on the side stream in front of the STFT, into a per-slot clip buffer.
+With `mixer` (a Mixer built on the same STFT) the bare STFT call becomes the mixer's: x is the clip mixed with other clips of the batch
+(the interferers are the clips after the audio transform), y stays the clip's own STFT.
 """
 import torch
 
 
 class ClipPipeline:
     def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None, audio_transform=None,
-                 audio_length=None):
+                 audio_length=None, mixer=None):
         self.va, self.stft, self.t = video_attention, stft, clip_frames
         self.transform = transform
         if audio_transform is None and audio_length is not None:
@@ -27,6 +29,9 @@ class ClipPipeline:
         if audio_transform is not None and (isinstance(audio_length, bool) or not isinstance(audio_length, int) or audio_length < 1):
             raise ValueError(f"audio_transform= needs audio_length=, the samples per clip after the transform, got {audio_length!r}")
         self.audio_transform, self.audio_length = audio_transform, audio_length
+        if mixer is not None and mixer.stft is not stft:
+            raise ValueError("mixer= must be built on the STFT object the pipeline is given")
+        self.mixer = mixer
         self.depth = depth
         self.finite_check = finite_check
         self.side = torch.cuda.Stream()
@@ -52,16 +57,35 @@ class ClipPipeline:
             raise ValueError(f"audio must be [B, C, L0] or [B, L0], got {tuple(getattr(audio, 'shape', ()))}")
         return self.audio_transform.check(audio, audio_sr, self.audio_length, batched=True)[0]
 
-    def submit(self, frames, audio, seed, boxes=None, audio_sr=None):
+    def check_mix(self, audio, raw_audio, seed, partners, snr_db):
+        """Host-side validation / seeded draw of submit()'s mixing arguments (no device work) -> (partners, snr_db) for the mixer, (None,
+        None) without one."""
+        if self.mixer is None:
+            if partners is not None or snr_db is not None:
+                raise ValueError("partners / snr_db need a ClipPipeline built with mixer=")
+            return None, None
+        # the clips the mixer will see: `audio` itself, or the [B, audio_length] buffer the audio transform is about to fill
+        clips = audio if raw_audio is None else (raw_audio.shape[0], self.audio_length)
+        if partners is None or snr_db is None:
+            drawn = self.mixer.sample(raw_audio.shape[0] if raw_audio is not None else audio.shape[0], torch.Generator().manual_seed(seed))
+            partners = drawn[0] if partners is None else partners
+            snr_db = drawn[1] if snr_db is None else snr_db
+        return self.mixer.check(clips, partners, snr_db)
+
+    def submit(self, frames, audio, seed, boxes=None, audio_sr=None, partners=None, snr_db=None):
         """Enqueue the extraction of one batch: frames [B*T,3,H,W], audio [B,L] (both resident on the device).  The caller's
         stream must already hold the work that produced them (the side stream waits for it).
         With a transform, frames are the uint8 clips [B*T,H0,W0,3] or [B,T,H0,W0,3] and `boxes` the CPU crop boxes [B,4]; by default
         transform.sample_boxes(B, H0, W0, torch.Generator().manual_seed(seed)), so a pipelined and a serial run see the same crops.
         With an audio_transform, audio is the raw clips [B,C,L0] or [B,L0] (f32 or int16) at `audio_sr` Hz; they must resample to at
-        least audio_length samples and are cropped to that."""
+        least audio_length samples and are cropped to that.
+        With a mixer, `partners` [B,K] int32 and `snr_db` [B] (CPU) choose the mixtures; by default
+        mixer.sample(B, torch.Generator().manual_seed(seed)), which is also what mixer(audio, seed=seed) draws: a pipelined and a serial
+        run see the same mixtures."""
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
         slot = self.slots[self.head % self.depth]
         raw_audio = self.check_audio(audio, audio_sr)                        # everything is validated before any device work
+        partners, snr_db = self.check_mix(audio, raw_audio, seed, partners, snr_db)
         if self.transform is not None:
             raw, _, boxes = self.transform.check(frames, boxes, self.t)
             f, h0, w0, _ = raw.shape
@@ -94,7 +118,10 @@ class ClipPipeline:
                 if slot["audio"] is None or slot["audio"].shape != (nb, self.audio_length):
                     slot["audio"] = torch.empty(nb, self.audio_length, device=audio.device, dtype=torch.float32)
                 audio = self.audio_transform(raw_audio, audio_sr, length=self.audio_length, out=slot["audio"])
-            slot["x"], slot["y"] = self.stft(audio, seed=seed)    # replaces (frees) the tensors of two batches ago, after the wait above
+            if self.mixer is not None:
+                slot["x"], slot["y"] = self.mixer(audio, partners, snr_db, seed=seed)
+            else:
+                slot["x"], slot["y"] = self.stft(audio, seed=seed)    # replaces (frees) the tensors of two batches ago, after the wait above
             slot["ready"].record(self.side)
         self.head += 1
 
