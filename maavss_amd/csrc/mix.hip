@@ -100,24 +100,17 @@ __global__ __launch_bounds__(MIX_THREADS) void mix_wave_kernel(const float* __re
 // stft_kernel no pair crosses a clip, so both frames share g_b, c_b and the partner rows, and a clip's result does not depend on its
 // neighbours in the launch.  A clip with g_b c_b = 0 skips the transform and copies y.
 // x0 = y + (g c) I, x = x0 + sigma * noise; sigma = 0 writes x0 itself, so x(sigma) - x(0) is the noise term to one rounding.
-// Noise counters: clip_absmax == null -> those of stft_kernel (block ((fid * 8 + jp) * 64 + lane) = re / im of bins lane + 128 jp and + 64 of
-// frame fid = b * n_frames + t; bin n_fft / 2: block (((fid & ~1) * 8 + 7) * 64), normals 2 (fid & 1) and 2 (fid & 1) + 1);
-// clip_absmax != null -> those of stft_normalise_kernel (block fid * n_bins_out + f, normal 0 = re, 1 = im).
+// Noise counters (stft_fft.h), fid = b * n_frames + t: clip_absmax == null -> those of stft_kernel, the last bin's taken per frame (block
+// stft_ctr_last of the launch's even frame, normals 2 (fid & 1) and 2 (fid & 1) + 1); clip_absmax != null -> those of stft_normalise_kernel.
 template <int NFFT, int FPB>
 __global__ __launch_bounds__(64 * FPB) void stft_mix_kernel(
     const float* __restrict__ pool, int64_t pool_stride, int n_pool, const int* __restrict__ partners, int k_slots, int length,
     const float* __restrict__ window, int hop, int n_frames, int n_bins_out, int batch, const float* __restrict__ y, float* __restrict__ x,
     const float* __restrict__ noise, float sigma, uint64_t seed, const float* __restrict__ gain, const float* __restrict__ clip_absmax) {
-  constexpr int NBUF = NFFT == 1024 ? 2 : 1;
-  __shared__ float2 buf[NBUF][FPB][NFFT];
+  __shared__ float2 buf[STFT_NBUF<NFFT>][FPB][NFFT];
   __shared__ float2 tw[NFFT];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int q = threadIdx.x; q < NFFT; q += blockDim.x) {
-    float s, c;
-    sincospif(-2.0f * (float)q / (float)NFFT, &s, &c);
-    tw[q] = make_float2(c, s);
-  }
-  __syncthreads();
+  stft_twiddles<NFFT>(tw);
   const int64_t plane = (int64_t)n_frames * n_bins_out;
   const int ppc = (n_frames + 1) / 2;                                   // pairs per clip
   const int npairs = batch * ppc;
@@ -135,17 +128,10 @@ __global__ __launch_bounds__(64 * FPB) void stft_mix_kernel(
     if (mix) {
       const float* rows[MIX_MAX_K];
       mix_rows(pool, pool_stride, n_pool, partners, k_slots, b, rows);
-      for (int n = lane; n < NFFT; n += 64) {
-        int j0 = t0 * hop + n - NFFT / 2, j1 = t1 * hop + n - NFFT / 2;
-        if (j0 < 0) j0 = -j0;
-        if (j0 >= length) j0 = 2 * (length - 1) - j0;
-        if (j1 < 0) j1 = -j1;
-        if (j1 >= length) j1 = 2 * (length - 1) - j1;
-        const float wn = window[n];
-        buf[0][wv][n] = make_float2(mix_gather(rows, j0) * wn, two_frames ? mix_gather(rows, j1) * wn : 0.f);
-      }
+      auto sample = [&](int j) { return mix_gather(rows, j); };
+      stft_load_pair<NFFT>(&buf[0][wv][0], window, lane, t0, t1, hop, length, two_frames, sample, sample);
       STFT_WAVE_SYNC();
-      cur = fft_forward<NFFT>(&buf[0][wv][0], &buf[NBUF - 1][wv][0], tw, lane);
+      cur = fft_forward<NFFT>(&buf[0][wv][0], &buf[STFT_NBUF<NFFT> - 1][wv][0], tw, lane);
     }
 #pragma unroll
     for (int fr = 0; fr < 2; ++fr) {
@@ -153,17 +139,12 @@ __global__ __launch_bounds__(64 * FPB) void stft_mix_kernel(
       const int t = fr ? t1 : t0;
       const int64_t fid = (int64_t)b * n_frames + t;
       const int64_t row = ((int64_t)b * 2) * plane + (int64_t)t * n_bins_out;
-      auto bin = [&](int f) __attribute__((always_inline)) {
-        if (!mix) return make_float2(0.f, 0.f);
-        const float2 z = buf[cur][wv][f], zn = buf[cur][wv][(NFFT - f) & (NFFT - 1)];
-        return fr == 0 ? make_float2(0.5f * (z.x + zn.x), 0.5f * (z.y - zn.y)) : make_float2(0.5f * (z.y + zn.y), -0.5f * (z.x - zn.x));
-      };
+      auto bin = [&](int f) __attribute__((always_inline)) { return mix ? stft_split<NFFT>(&buf[cur][wv][0], f, fr) : make_float2(0.f, 0.f); };
       auto put = [&](int64_t o, float2 v, float nre, float nim) __attribute__((always_inline)) {
         const float yre = y[o], yim = y[o + plane];
-        // written as stft_kernel writes its own x (v + sigma * g), so that the compiler contracts both alike
         const float re = mix ? yre + gc * v.x : yre, im = mix ? yim + gc * v.y : yim;
-        x[o] = add_noise ? re + sigma * nre : re;
-        x[o + plane] = add_noise ? im + sigma * nim : im;
+        x[o] = add_noise ? stft_add_noise(re, sigma, nre) : re;
+        x[o + plane] = add_noise ? stft_add_noise(im, sigma, nim) : im;
       };
       for (int f0 = lane, jp = 0; f0 < n_low; f0 += 128, ++jp) {
         const int f1 = f0 + 64;
@@ -171,24 +152,12 @@ __global__ __launch_bounds__(64 * FPB) void stft_mix_kernel(
         const int64_t o0 = row + f0;
         float g[4] = {0.f, 0.f, 0.f, 0.f};
         if (noise != nullptr) {
-          g[0] = noise[o0];
-          g[1] = noise[o0 + plane];
-          g[2] = two ? noise[o0 + 64] : 0.f;
-          g[3] = two ? noise[o0 + 64 + plane] : 0.f;
+          stft_noise_given(g, noise, o0, plane, two);
+        } else if (gen && !normalised) {
+          philox_normal4(seed, stft_ctr_pair(fid, jp, lane), g);
         } else if (gen) {
-          if (!normalised) {
-            philox_normal4(seed, ((uint64_t)fid * 8 + jp) * 64 + lane, g);
-          } else {
-            float h[4];
-            philox_normal4(seed, (uint64_t)fid * n_bins_out + f0, h);
-            g[0] = h[0];
-            g[1] = h[1];
-            if (two) {
-              philox_normal4(seed, (uint64_t)fid * n_bins_out + f1, h);
-              g[2] = h[0];
-              g[3] = h[1];
-            }
-          }
+          stft_noise_bin(g[0], g[1], seed, stft_ctr_bin(fid, n_bins_out, f0));
+          if (two) stft_noise_bin(g[2], g[3], seed, stft_ctr_bin(fid, n_bins_out, f1));
         }
         put(o0, bin(f0), g[0], g[1]);
         if (two) put(o0 + 64, bin(f1), g[2], g[3]);
@@ -199,17 +168,13 @@ __global__ __launch_bounds__(64 * FPB) void stft_mix_kernel(
         if (noise != nullptr) {
           nre = noise[o];
           nim = noise[o + plane];
-        } else if (gen) {
+        } else if (gen && !normalised) {
           float h[4];
-          if (!normalised) {
-            philox_normal4(seed, ((uint64_t)(fid & ~(int64_t)1) * 8 + 7) * 64, h);
-            nre = (fid & 1) ? h[2] : h[0];
-            nim = (fid & 1) ? h[3] : h[1];
-          } else {
-            philox_normal4(seed, (uint64_t)fid * n_bins_out + NFFT / 2, h);
-            nre = h[0];
-            nim = h[1];
-          }
+          philox_normal4(seed, stft_ctr_last(fid & ~(int64_t)1), h);
+          nre = (fid & 1) ? h[2] : h[0];
+          nim = (fid & 1) ? h[3] : h[1];
+        } else if (gen) {
+          stft_noise_bin(nre, nim, seed, stft_ctr_bin(fid, n_bins_out, NFFT / 2));
         }
         put(o, bin(NFFT / 2), nre, nim);
       }
@@ -270,26 +235,20 @@ extern "C" int maavss_stft_mix_fwd(const float* pool, int64_t n_pool, int64_t le
                                    const float* y, float* x, const float* noise, float sigma, uint64_t seed, const float* gain,
                                    const float* clip_absmax, void* stream) {
   if (int rc = mix_check_common("stft_mix", pool, pool_stride, n_pool, partners, k_slots, batch, length)) return rc;
-  MAAVSS_CHECK_ARG(n_fft == 256 || n_fft == 512 || n_fft == 1024, "stft_mix: n_fft must be 256, 512 or 1024 (got %d)", n_fft);
   MAAVSS_CHECK_ARG(window && y && x && gain, "stft_mix: null pointer");
-  MAAVSS_CHECK_ARG(hop > 0 && n_frames > 0, "stft_mix: empty problem");
-  MAAVSS_CHECK_ARG(n_bins_out >= 1 && n_bins_out <= n_fft / 2 + 1, "stft_mix: n_bins_out out of range");
+  if (int rc = stft_check_frames("stft_mix", n_fft, hop, n_frames, n_bins_out, length)) return rc;
   const int64_t spec = batch * 2 * n_frames * n_bins_out;
   MAAVSS_CHECK_ARG(!mix_overlap(x, spec, y, spec) && !mix_overlap(x, spec, pool, mix_extent(n_pool, pool_stride, length)) &&
                        (noise == nullptr || !mix_overlap(x, spec, noise, spec)),
                    "stft_mix: x overlaps y, noise or pool (they are read while x is written)");
-  MAAVSS_CHECK_ARG(length > n_fft / 2, "stft_mix: reflect padding needs length > n_fft/2");
-  MAAVSS_CHECK_ARG((int64_t)(n_frames - 1) * hop + n_fft / 2 - 1 < 2 * length - 1, "stft_mix: frames run past the reflected signal");
   MAAVSS_CHECK_ARG(batch * ((int64_t)n_frames + 1) < INT32_MAX, "stft_mix: too many frames for one launch");
   const int npairs = (int)(batch * ((n_frames + 1) / 2));
   hipStream_t st = (hipStream_t)stream;
 #define LAUNCH(N, FPB)                                                                                                                      \
-  hipLaunchKernelGGL((stft_mix_kernel<N, FPB>), dim3(cdiv(npairs, FPB) < 2048 ? cdiv(npairs, FPB) : 2048), dim3(64 * FPB), 0, st, pool,       \
-                     pool_stride, (int)n_pool, partners, k_slots, (int)length, window, hop, n_frames, n_bins_out, (int)batch, y, x, noise, \
-                     sigma, seed, gain, clip_absmax)
-  if (n_fft == 256) LAUNCH(256, 4);
-  else if (n_fft == 512) LAUNCH(512, 4);
-  else LAUNCH(1024, 2);
+  hipLaunchKernelGGL((stft_mix_kernel<N, FPB>), dim3(stft_pair_grid(npairs, FPB)), dim3(64 * FPB), 0, st, pool, pool_stride, (int)n_pool, \
+                     partners, k_slots, (int)length, window, hop, n_frames, n_bins_out, (int)batch, y, x, noise, sigma, seed, gain,        \
+                     clip_absmax)
+  STFT_DISPATCH(n_fft, LAUNCH);
 #undef LAUNCH
   MAAVSS_LAUNCH_CHECK("stft_mix_kernel");
   return MAAVSS_OK;

@@ -1,45 +1,26 @@
 // K17: audio STFT (+ noise) -- replaces AV_Dataset.stft / gen_stft_example / add_noise
 // (reference av_dataset.py:157-174, 217-220, 335-342).
 //
-// One wavefront per STFT frame: reflect-padded framing + (pre-scaled) periodic Hamming window are
-// applied while the frame is loaded into LDS, a radix-2 Stockham FFT runs in LDS (ping-pong
-// buffers, twiddles from an LDS table), and the one-sided bins are written straight into the
-// [B, 2, T_a, F] (re/im plane, frame, bin) layout the model consumes, together with the noisy
-// copy x = y + sigma * N(0,1).  HBM-bound: 4*L bytes in, 2 * 2*T_a*F*4 bytes out per clip.
+// One wavefront per PAIR of consecutive frames of the launch's frame list (a pair may straddle two clips), on a grid-stride list of pairs:
+// reflect-padded framing + (pre-scaled) periodic Hamming window are applied while the two frames are loaded into LDS as one complex frame,
+// a radix-8 / radix-4 Stockham FFT runs in LDS with its butterflies in registers (twiddles from an LDS table), and the two one-sided
+// spectra are separated and written straight into the [B, 2, T_a, F] (re/im plane, frame, bin) layout the model consumes, together with the
+// noisy copy x = y + sigma * N(0,1) and each clip's max|y|.  4*L bytes in, 2 * 2*T_a*F*4 bytes out per clip.
+// Framing, transform, split and noise counters are stft_fft.h's, shared with mix.hip; why they are built this way is told there.
 #include "common.h"
 #include "stft_fft.h"
 
-
-// Round 3: (1) the waves of a workgroup are independent, so the FFT stages are ordered by the wave's own LDS queue (LDS operations of
-// one wave complete in issue order) and a compiler-level wave barrier instead of ten workgroup barriers per frame; (2) a workgroup
-// builds its twiddle table once and walks a grid-stride list of frame PAIRS; (3) two real frames share one complex FFT (z = a + i b,
-// A[k] = (Z[k] + conj Z[N-k]) / 2, B[k] = (Z[k] - conj Z[N-k]) / 2i): half the butterflies and LDS passes per frame; (4) one Philox
-// block serves two bins (its four normals: re / im of bins f and f + 64) instead of one.  profiles/r3_stft_bench.json.
-// Round 4: the Stockham FFT runs in radix-8 / radix-4 passes (512 = 8.8.8, 256 = 4.4.4.4, 1024 = 8.8.4.4) with the butterflies in registers:
-// three LDS round trips per frame pair instead of nine, 69 LDS instructions per lane instead of 180, ~270 vector instructions instead of ~900
-// (the kernel is bound by its vector work, not by HBM: DESIGN.md); Box-Muller takes its angle through v_sin_f32 / v_cos_f32, whose argument
-// is in revolutions -- exactly the uniform deviate -- instead of sincospif's software range reduction.  profiles/r4_stft_bench.json.
-// STFT_WAVE_SYNC, the register butterflies, fft_pass and fft_forward: stft_fft.h
-// In-kernel noise, counter layout (Philox4x32-10 block = four normals): block ((fid * 8 + jp) * 64 + lane) = re / im of bins f0 = lane + 128 jp and
-// f0 + 64 of frame fid, for the bins below n_fft / 2; the LAST bin (n_fft / 2, present when n_bins_out = n_fft / 2 + 1) of both frames of a pair
-// takes block ((fid0 * 8 + 7) * 64) = (re, im) of frame fid0, (re, im) of frame fid0 + 1.  A wave evaluates that block for its next 64 pairs
-// in one call (lane k = the pair of iteration k) and hands the values out by v_readlane -- round 4: as a third pass of the bin loop the one
-// extra bin cost a whole wave-wide Philox call per frame, a third of the kernel's generator work.
+// The last bin's noise: a wave evaluates block stft_ctr_last for its next 64 pairs in one call (lane k = the pair of iteration k) and hands the values out by
+// v_readlane -- round 4: as a third pass of the bin loop the one extra bin cost a whole wave-wide Philox call per frame, a third of the kernel's generator work.
 template <int NFFT, int STFT_FPB>
 __global__ __launch_bounds__(64 * STFT_FPB) void stft_kernel(
     const float* __restrict__ audio, int64_t audio_stride, int length, const float* __restrict__ window, int hop,
     int n_frames, int n_bins_out, int total_frames, float* __restrict__ y, float* __restrict__ x,
     const float* __restrict__ noise, float sigma, uint64_t seed, float* __restrict__ clip_absmax) {
-  constexpr int NBUF = NFFT == 1024 ? 2 : 1;     // 512 / 256 points transform in place
-  __shared__ float2 buf[NBUF][STFT_FPB][NFFT];
-  __shared__ float2 tw[NFFT];                    // exp(-2 pi i q / N) for q < N (the radix-8 / radix-4 passes index up to 7 k N / (8 P) < N)
+  __shared__ float2 buf[STFT_NBUF<NFFT>][STFT_FPB][NFFT];
+  __shared__ float2 tw[NFFT];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int q = threadIdx.x; q < NFFT; q += blockDim.x) {
-    float s, c;
-    sincospif(-2.0f * (float)q / (float)NFFT, &s, &c);
-    tw[q] = make_float2(c, s);
-  }
-  __syncthreads();
+  stft_twiddles<NFFT>(tw);
   const int64_t plane = (int64_t)n_frames * n_bins_out;
   const int npairs = (total_frames + 1) / 2;
   const int n_low = n_bins_out < NFFT / 2 ? n_bins_out : NFFT / 2;      // bins served by the paired blocks
@@ -51,7 +32,7 @@ __global__ __launch_bounds__(64 * STFT_FPB) void stft_kernel(
   for (int pid = blockIdx.x * STFT_FPB + wv; pid < npairs; pid += pid_step, ++it) {
     if (gen_last && (it & 63) == 0) {
       const int64_t pk = (int64_t)pid + (int64_t)lane * pid_step;       // the pair of iteration it + lane
-      philox_normal4(seed, ((uint64_t)(2 * pk) * 8 + 7) * 64, nyq);
+      philox_normal4(seed, stft_ctr_last(2 * pk), nyq);
     }
     const int fid0 = 2 * pid, fid1 = fid0 + 1;
     const bool two_frames = fid1 < total_frames;
@@ -59,17 +40,9 @@ __global__ __launch_bounds__(64 * STFT_FPB) void stft_kernel(
     const int b1 = two_frames ? fid1 / n_frames : b0, t1 = two_frames ? fid1 % n_frames : t0;
     const float* a0 = audio + (int64_t)b0 * audio_stride;
     const float* a1 = audio + (int64_t)b1 * audio_stride;
-    for (int n = lane; n < NFFT; n += 64) {
-      int j0 = t0 * hop + n - NFFT / 2, j1 = t1 * hop + n - NFFT / 2;
-      if (j0 < 0) j0 = -j0;
-      if (j0 >= length) j0 = 2 * (length - 1) - j0;
-      if (j1 < 0) j1 = -j1;
-      if (j1 >= length) j1 = 2 * (length - 1) - j1;
-      const float wn = window[n];
-      buf[0][wv][n] = make_float2(a0[j0] * wn, two_frames ? a1[j1] * wn : 0.f);
-    }
+    stft_load_pair<NFFT>(&buf[0][wv][0], window, lane, t0, t1, hop, length, two_frames, [&](int j) { return a0[j]; }, [&](int j) { return a1[j]; });
     STFT_WAVE_SYNC();
-    const int cur = fft_forward<NFFT>(&buf[0][wv][0], &buf[NBUF - 1][wv][0], tw, lane);
+    const int cur = fft_forward<NFFT>(&buf[0][wv][0], &buf[STFT_NBUF<NFFT> - 1][wv][0], tw, lane);
     // ---- separate the two spectra and write them (+ the noisy copies); `fr` = 0 / 1 selects the frame of the pair
 #pragma unroll
     for (int fr = 0; fr < 2; ++fr) {
@@ -79,10 +52,7 @@ __global__ __launch_bounds__(64 * STFT_FPB) void stft_kernel(
       float* yre = y + row;
       float* yim = yre + plane;
       float amax = 0.f;
-      auto bin = [&](int f) __attribute__((always_inline)) {
-        const float2 z = buf[cur][wv][f], zn = buf[cur][wv][(NFFT - f) & (NFFT - 1)];
-        return fr == 0 ? make_float2(0.5f * (z.x + zn.x), 0.5f * (z.y - zn.y)) : make_float2(0.5f * (z.y + zn.y), -0.5f * (z.x - zn.x));
-      };
+      auto bin = [&](int f) __attribute__((always_inline)) { return stft_split<NFFT>(&buf[cur][wv][0], f, fr); };
       // bins in pairs (f, f + 64): one Philox block = four normals = the noise of both
       for (int f0 = lane, jp = 0; f0 < n_low; f0 += 128, ++jp) {
         const int f1 = f0 + 64;
@@ -95,19 +65,13 @@ __global__ __launch_bounds__(64 * STFT_FPB) void stft_kernel(
         if (x != nullptr) {
           const int64_t o0 = row + f0;
           float g[4];
-          if (noise != nullptr) {
-            g[0] = noise[o0];
-            g[1] = noise[o0 + plane];
-            g[2] = two ? noise[o0 + 64] : 0.f;
-            g[3] = two ? noise[o0 + 64 + plane] : 0.f;
-          } else {
-            philox_normal4(seed, ((uint64_t)fid * 8 + jp) * 64 + lane, g);
-          }
-          x[o0] = v0.x + sigma * g[0];
-          x[o0 + plane] = v0.y + sigma * g[1];
+          if (noise != nullptr) stft_noise_given(g, noise, o0, plane, two);
+          else philox_normal4(seed, stft_ctr_pair(fid, jp, lane), g);
+          x[o0] = stft_add_noise(v0.x, sigma, g[0]);
+          x[o0 + plane] = stft_add_noise(v0.y, sigma, g[1]);
           if (two) {
-            x[o0 + 64] = v1.x + sigma * g[2];
-            x[o0 + 64 + plane] = v1.y + sigma * g[3];
+            x[o0 + 64] = stft_add_noise(v1.x, sigma, g[2]);
+            x[o0 + 64 + plane] = stft_add_noise(v1.y, sigma, g[3]);
           }
         }
       }
@@ -122,8 +86,8 @@ __global__ __launch_bounds__(64 * STFT_FPB) void stft_kernel(
           yim[NFFT / 2] = v.y;
           amax = fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y)));
           if (x != nullptr) {
-            x[o] = v.x + sigma * (noise != nullptr ? noise[o] : gre);
-            x[o + plane] = v.y + sigma * (noise != nullptr ? noise[o + plane] : gim);
+            x[o] = stft_add_noise(v.x, sigma, noise != nullptr ? noise[o] : gre);
+            x[o + plane] = stft_add_noise(v.y, sigma, noise != nullptr ? noise[o + plane] : gim);
           }
         }
       }
@@ -153,12 +117,12 @@ __global__ void stft_normalise_kernel(float* __restrict__ y, float* __restrict__
         const int64_t r = i - b * per_clip;
         const int64_t plane = (int64_t)n_frames * n_bins_out;
         const int pl = (int)(r / plane);
-        const int64_t tf = r - pl * plane;  // t * n_bins + f
+        const int64_t tf = r - pl * plane;  // t * n_bins + f: the clip's first frame below, the counter is linear in both
         float g[4];
-        philox_normal4(seed, (uint64_t)(b * n_frames) * n_bins_out + tf, g);
+        philox_normal4(seed, stft_ctr_bin(b * n_frames, n_bins_out, tf), g);
         nz = g[pl];
       }
-      x[i] = v + sigma * nz;
+      x[i] = stft_add_noise(v, sigma, nz);
     }
   }
 }
@@ -167,21 +131,15 @@ extern "C" int maavss_stft_fwd(const float* audio, int64_t batch, int64_t length
                                const float* window, int n_fft, int hop, int n_frames, int n_bins_out, float* y,
                                float* x, const float* noise, float sigma, uint64_t seed, float* clip_absmax,
                                void* stream) {
-  MAAVSS_CHECK_ARG(n_fft == 256 || n_fft == 512 || n_fft == 1024, "stft: n_fft must be 256, 512 or 1024 (got %d)", n_fft);
   MAAVSS_CHECK_ARG(audio && window && y, "stft: null pointer");
-  MAAVSS_CHECK_ARG(batch > 0 && hop > 0 && n_frames > 0, "stft: empty problem");
-  MAAVSS_CHECK_ARG(n_bins_out >= 1 && n_bins_out <= n_fft / 2 + 1, "stft: n_bins_out out of range");
-  MAAVSS_CHECK_ARG(length > n_fft / 2, "stft: reflect padding needs length > n_fft/2");
-  MAAVSS_CHECK_ARG((int64_t)(n_frames - 1) * hop + n_fft / 2 - 1 < 2 * length - 1, "stft: frames run past the reflected signal");
+  MAAVSS_CHECK_ARG(batch > 0, "stft: empty problem");
+  if (int rc = stft_check_frames("stft", n_fft, hop, n_frames, n_bins_out, length)) return rc;
   const int total = (int)(batch * n_frames);
   hipStream_t st = (hipStream_t)stream;
-  // grid-stride over the frames: at most 8 workgroups per CU worth of blocks (the twiddle table is built once per workgroup)
-#define LAUNCH(N, FPB)                                                                                         \
-  hipLaunchKernelGGL((stft_kernel<N, FPB>), dim3(cdiv(cdiv(total, 2), FPB) < 2048 ? cdiv(cdiv(total, 2), FPB) : 2048), dim3(64 * FPB), 0, st, audio, audio_stride, \
+#define LAUNCH(N, FPB)                                                                                                                 \
+  hipLaunchKernelGGL((stft_kernel<N, FPB>), dim3(stft_pair_grid(cdiv(total, 2), FPB)), dim3(64 * FPB), 0, st, audio, audio_stride, \
                      (int)length, window, hop, n_frames, n_bins_out, total, y, x, noise, sigma, seed, clip_absmax)
-  if (n_fft == 256) LAUNCH(256, 4);
-  else if (n_fft == 512) LAUNCH(512, 4);
-  else LAUNCH(1024, 2);
+  STFT_DISPATCH(n_fft, LAUNCH);
 #undef LAUNCH
   MAAVSS_LAUNCH_CHECK("stft_kernel");
   return MAAVSS_OK;
@@ -278,7 +236,7 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
 
 extern "C" int maavss_istft(const float* spec, int64_t batch, int n_frames, int n_bins_in, const float* window, int n_fft,
                             int hop, int normalized, float* frames_ws, float* audio, int64_t audio_stride, void* stream) {
-  MAAVSS_CHECK_ARG(n_fft == 256 || n_fft == 512 || n_fft == 1024, "istft: n_fft must be 256, 512 or 1024 (got %d)", n_fft);
+  STFT_CHECK_N_FFT("istft", n_fft);
   MAAVSS_CHECK_ARG(spec && window && frames_ws && audio, "istft: null pointer");
   MAAVSS_CHECK_ARG(batch > 0 && hop > 0 && n_frames > 1, "istft: needs at least two frames");
   MAAVSS_CHECK_ARG(n_bins_in == n_fft / 2 || n_bins_in == n_fft / 2 + 1, "istft: n_bins must be n_fft/2 (trimmed) or n_fft/2+1");
@@ -292,9 +250,7 @@ extern "C" int maavss_istft(const float* spec, int64_t batch, int n_frames, int 
 #define LAUNCH(N, FPB)                                                                                                   \
   hipLaunchKernelGGL((istft_frames_kernel<N, FPB>), dim3(cdiv(total, FPB)), dim3(64 * FPB), 0, st, spec, window, n_frames, \
                      n_bins_in, total, scale, frames_ws)
-  if (n_fft == 256) LAUNCH(256, 4);
-  else if (n_fft == 512) LAUNCH(512, 4);
-  else LAUNCH(1024, 2);
+  STFT_DISPATCH(n_fft, LAUNCH);
 #undef LAUNCH
   MAAVSS_LAUNCH_CHECK("istft_frames_kernel");
   const int64_t n_out = batch * out_len;
