@@ -10,6 +10,7 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --raw_video 360x640 [--autocontrast]   # decoded uint8 clips through VideoTransform first
     python examples/train_synthetic.py --raw_audio [--compress_audio]         # 44.1 kHz stereo int16 clips through AudioTransform first
     python examples/train_synthetic.py --mix 2 --mix_snr 0 10                 # mix-and-separate: every clip + 2 others of the batch at 0..10 dB
+    python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
 """
 import argparse
 import os
@@ -44,6 +45,10 @@ def main():
     ap.add_argument("--mix", type=int, default=0, metavar="K",
                     help="mix-and-separate: add K other clips of the batch (1..4) to every clip's input; each clip is its own set of sinusoids")
     ap.add_argument("--mix_snr", type=float, nargs=2, default=(0.0, 10.0), metavar=("LO", "HI"), help="with --mix: signal-to-interferer range in dB")
+    ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM",
+                    help="clip the global gradient norm (clip_grad_norm_'s rule, on the device: TrainStep(max_grad_norm=...))")
+    ap.add_argument("--watch", type=int, default=0, metavar="N",
+                    help="every N steps, the per-tensor gradient / parameter histograms wandb.watch would log (maavss_amd.ModelWatch)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
@@ -54,7 +59,8 @@ def main():
     extractor = maavss_amd.VideoAttention(path_to_weights="dino_deitsmall8_pretrain.pth")      # random init when absent (no network)
     stft = maavss_amd.STFT(a.fft_len, hop, noise_std=0.1, device=dev)
     model = maavss_amd.AV_Fusion_Model_Frames([b, 2, hpf * nf, n_bins], [b, 1, nf, w, w], hpf, precise=a.precise).to(dev).train()
-    step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns)
+    step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip)
+    watch = maavss_amd.ModelWatch(step, log_freq=a.watch) if a.watch else None
     transform = None
     if a.raw_video:
         h0, w0 = (int(v) for v in a.raw_video.lower().split("x"))
@@ -99,8 +105,16 @@ def main():
         attn, x_stft, y_stft = pipe.get()                        # [B,1,T,H,W], [B,2,T_a,F] x 2
         losses = step.sliding_window_step(x_stft, y_stft, attn, attn, nf, hpf)
         pipe.release()
+        logs = watch.after_step() if watch is not None else None
         if i % a.log_every == 0 or i == a.steps - 1:
-            print(f"step {i}: a_loss {losses[0].item():.5f}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}", flush=True)
+            clip = "" if a.clip is None else f"  |g| {step.opt.grad_norm.item():.4g}  scale {step.opt.clip_scale.item():.4g}"
+            print(f"step {i}: a_loss {losses[0].item():.5f}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}", flush=True)
+        if logs is not None:
+            # with wandb: wandb.log({k: wandb.Histogram(np_histogram=v) for k, v in logs.items() if not k.startswith("nonfinite/")})
+            bad = [k for k in logs if k.startswith("nonfinite/")]
+            counts, edges = logs["gradients/fc2.weight"]
+            print(f"step {i}: {len(logs) - len(bad)} histograms; gradients/fc2.weight in [{edges[0]:.3g}, {edges[-1]:.3g}], fullest bin "
+                  f"{int(counts.argmax())} of {len(counts)}; tensors with non-finite values: {len(bad)}", flush=True)
     pipe.drain()
 
     with tempfile.TemporaryDirectory() as cp_dir:

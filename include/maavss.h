@@ -294,6 +294,43 @@ int maavss_mse_pair(const float* a_pred, const float* a_tgt, int64_t na, const f
                     void* stream);
 int maavss_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                      float eps, int64_t step, float grad_scale, void* stream);
+/* adam_step_dscale: maavss_adam_step with the gradient scale read from device memory (one f32, 4-byte aligned) by the same kernel
+ * body -- the clip scale maavss_tensor_stats wrote earlier on the stream, so that clipping costs no host synchronisation.  Same
+ * arithmetic: with *grad_scale_dev == grad_scale the results are bit-identical to maavss_adam_step's. */
+int maavss_adam_step_dscale(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                            float eps, int64_t step, const float* grad_scale_dev, void* stream);
+
+/* ---- EXTENSION: per-tensor statistics of a flat f32 buffer (maavss_amd.TensorStats, gradient-norm clipping, ModelWatch) ------
+ * What torch.nn.utils.clip_grad_norm_ and wandb.watch(model, log="all") (train_avse_frames.py:108) compute through autograd hooks,
+ * for the autograd-free step: one segmented reduction over the flat gradient (or parameter) buffer.  Added without a version bump.
+ *   segment s = one tensor, elements [host_seg_offset[s], + host_seg_numel[s]) of buf [n] (buf 16-byte aligned; numel < 2^31);
+ *   chunks [n_chunks][3] int64 on the DEVICE: (segment, first element, length) -- every segment cut, in buffer order, into
+ *   ceil(numel / CH) pieces of at most CH = maavss_tensor_stats_chunk() elements; seg_first [n_segments + 1] int32 on the device:
+ *   the rows of segment s are seg_first[s] .. seg_first[s + 1].  A row outside the buffer is read as empty.
+ *   seg_mask [n_segments] int32 (nullable = all): the segments that count towards total_sumsq / norm / scale.
+ * Per segment: sumsq f64 = sum of the squares of the FINITE elements (squares exact, accumulated in f64 in a fixed order: within
+ * (numel - 1) * 2^-53 relative of the exact sum), seg_min / seg_max f32 over the finite elements (NaN when there is none),
+ * nonfinite [n_segments][3] int32 = counts of NaN, +inf, -inf.
+ * max_norm >= 0 requests a clip: total_sumsq f64 = sum of sumsq over the selected segments; with
+ *   norm64 = sqrt(total_sumsq) * grad_scale (f64), norm = (float)norm64, scale = (float)(grad_scale * min(1, max_norm / (norm64 + 1e-6)))
+ * -- clip_grad_norm_'s coefficient for the gradient after grad_scale, times grad_scale: what maavss_adam_step_dscale multiplies g by.
+ * A NaN in a selected segment makes norm and scale NaN, otherwise an inf makes norm +inf and scale 0 (error_if_nonfinite=False).
+ * max_norm < 0: total_sumsq / norm / scale are not written (and may be null).
+ * hist (nullable) [n_segments][bins] int32, 1 <= bins <= 1024: torch.histc(x, bins) of the finite elements of each segment between
+ * its min and max ([lo - 1, hi + 1] when they are equal): element x counts in bin (int)((x - lo) * (float)bins / (hi - lo)) evaluated
+ * in f32 with one rounding per operation, bins -> bins - 1.
+ * ws: maavss_tensor_stats_ws_bytes(n_chunks, n_segments, bins) bytes, 8-byte aligned =
+ *   round256(32 * n_chunks) [one {f64 sumsq, f32 min, f32 max, int32 nan, +inf, -inf, pad} per chunk] + round256(8 * n_segments)
+ *   [the selected sums]; `bins` is range-checked only (0 for an invalid argument): the counts are accumulated in hist itself.
+ * Launches: pass 1 (one workgroup per chunk), finalize (one workgroup), and with hist a second pass over buf.  No floating-point
+ * atomics: every output is bit-identical from run to run. */
+int maavss_tensor_stats_chunk(void);
+int64_t maavss_tensor_stats_ws_bytes(int64_t n_chunks, int64_t n_segments, int bins);
+int maavss_tensor_stats(const float* buf, int64_t n, const int64_t* chunks, int64_t n_chunks, const int* seg_first,
+                        const int64_t* host_seg_offset, const int64_t* host_seg_numel, int64_t n_segments, const int* seg_mask,
+                        double* sumsq, float* seg_min, float* seg_max, int* nonfinite, int* hist, int bins, double max_norm,
+                        float grad_scale, double* total_sumsq, float* norm, float* scale, void* ws, int64_t ws_bytes, void* stream);
+
 /* K18 helper, EXTENSION (the reference is single-device): bf16 wire format of the data-parallel gradient all-reduce -- a bucket of
  * the flat f32 gradient buffer is rounded to bf16 (round-to-nearest-even) for the collective and widened back into the f32 master
  * buffer afterwards (trainer.GradSync(wire_dtype="bf16")).  n a multiple of 8, buffers 16-byte aligned. */

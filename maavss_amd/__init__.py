@@ -16,6 +16,7 @@ from .video_transform import VideoTransform  # noqa: F401
 from .audio_transform import AudioTransform  # noqa: F401
 from .enhance import Enhancer  # noqa: F401
 from .mixer import Mixer  # noqa: F401
+from .tensor_stats import ModelWatch, TensorStats, plan_chunks  # noqa: F401
 
 from . import attn_cache  # noqa: F401
 

@@ -43,9 +43,10 @@ __global__ void mse_finalize_kernel(const float* __restrict__ pa, int na_blk, do
   losses[2] = (float)((la + (double)coeff * lv) * (double)inv_num_seq);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n4, int64_t n, float lr_bc1, float b1,
-                                                   float b2, float eps, float inv_sqrt_bc2, float gscale) {
+// one Adam update of the range: shared by adam_kernel (scale from the launch arguments) and adam_dscale_kernel (scale read from memory)
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                          int64_t n4, int64_t n, float lr_bc1, float b1, float b2, float eps, float inv_sqrt_bc2,
+                                          float gscale) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     float4 pp = reinterpret_cast<float4*>(p)[i];
     float4 gg = reinterpret_cast<const float4*>(g)[i];
@@ -71,6 +72,19 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       p[i] -= lr_bc1 * m[i] / (sqrtf(v[i]) * inv_sqrt_bc2 + eps);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n4, int64_t n, float lr_bc1, float b1,
+                                                   float b2, float eps, float inv_sqrt_bc2, float gscale) {
+  adam_body(p, g, m, v, n4, n, lr_bc1, b1, b2, eps, inv_sqrt_bc2, gscale);
+}
+
+// the gradient scale is a device scalar (the clip scale maavss_tensor_stats wrote earlier on the stream): read once per thread
+__global__ __launch_bounds__(256) void adam_dscale_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, int64_t n4, int64_t n, float lr_bc1, float b1,
+                                                          float b2, float eps, float inv_sqrt_bc2, const float* __restrict__ gscale_dev) {
+  adam_body(p, g, m, v, n4, n, lr_bc1, b1, b2, eps, inv_sqrt_bc2, *gscale_dev);
 }
 
 // EXTENSION (not in the reference): AdaptiveAvgPool2d that ends the STFT encoder when the frame size is
@@ -143,6 +157,18 @@ extern "C" int maavss_adam_step(float* p, const float* g, float* m, float* v, in
   hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, n, (float)(lr / bc1),
                      beta1, beta2, eps, (float)(1.0 / sqrt(bc2)), grad_scale);
   MAAVSS_LAUNCH_CHECK("adam_kernel");
+  return MAAVSS_OK;
+}
+
+extern "C" int maavss_adam_step_dscale(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                       float eps, int64_t step, const float* grad_scale_dev, void* stream) {
+  MAAVSS_CHECK_ARG(p && g && m && v && grad_scale_dev && n > 0 && step >= 1, "adam_step_dscale: bad arguments");
+  MAAVSS_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step_dscale: buffers must be 16-byte aligned");
+  MAAVSS_CHECK_ARG(((uintptr_t)grad_scale_dev & 3) == 0, "adam_step_dscale: grad_scale_dev must be 4-byte aligned");
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adam_dscale_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, n, (float)(lr / bc1),
+                     beta1, beta2, eps, (float)(1.0 / sqrt(bc2)), grad_scale_dev);
+  MAAVSS_LAUNCH_CHECK("adam_dscale_kernel");
   return MAAVSS_OK;
 }
 

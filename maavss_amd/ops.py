@@ -529,6 +529,13 @@ def adam_step(p, g, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0
          float(eps), int(step), float(grad_scale), stream_ptr())
 
 
+def adam_step_dscale(p, g, m, v, lr, step, grad_scale_dev, betas=(0.9, 0.999), eps=1e-8):
+    """adam_step with the gradient scale read from the device scalar `grad_scale_dev` (f32 [1]) by the kernel."""
+    _f32(p, g, m, v, grad_scale_dev)
+    call("maavss_adam_step_dscale", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+         float(eps), int(step), ptr(grad_scale_dev), stream_ptr())
+
+
 def f32_to_bf16(src, dst):
     """bf16 wire format of the gradient all-reduce: dst (bf16) = round(src (f32)); length a multiple of 8."""
     _lib.require_cuda(src, dst)

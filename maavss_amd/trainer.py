@@ -95,11 +95,25 @@ class FusedAdam:
     """torch.optim.Adam semantics (betas .9/.999, eps 1e-8, no weight decay, no amsgrad) in HIP launches over the flat
     buffers.  Like torch, a parameter is only stepped when a backward pass produced a gradient for it since the last
     zero_grad() (frozen sub-networks and stft_decoder.* under forward() are left alone, keep their moments and their
-    own step count); contiguous runs of stepped parameters share one launch -- one launch in the usual case."""
+    own step count); contiguous runs of stepped parameters share one launch -- one launch in the usual case.
 
-    def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    `max_grad_norm` (None = off: the launches are exactly the ones above) clips the global 2-norm of the gradient the way
+    `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` does before `optimizer.step()`, over exactly the parameters this step
+    updates (touched and requires_grad, as torch clips those whose .grad is not None): one segmented reduction over the flat
+    gradient buffer (tensor_stats.TensorStats) leaves the norm and the coefficient on the device and the Adam kernel reads the
+    coefficient from there -- no host synchronisation.  Unlike torch, the gradients are NOT rescaled in memory: `flat.grads` keeps the
+    unclipped values, the scale is applied inside the Adam kernel.  `grad_norm` (the norm of grad_scale * g) and `clip_scale`
+    (grad_scale * min(1, max_grad_norm / (norm + 1e-6))) are the device scalars of the last step; a non-finite gradient makes them
+    NaN (any NaN) or +inf / 0 (an inf, no NaN), as torch's error_if_nonfinite=False -- the caller decides when to look."""
+
+    def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else FlatParams(model_or_flat)
         self.lr, self.betas, self.eps = lr, betas, eps
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError("max_grad_norm must be None or >= 0")
+        self.max_grad_norm = max_grad_norm
+        self.grad_stats = None                  # tensor_stats.TensorStats over flat.grads, built by the first clipped step
+        self.grad_norm = self.clip_scale = None
         self.exp_avg = torch.zeros_like(self.flat.params)
         self.exp_avg_sq = torch.zeros_like(self.flat.params)
         self.steps = {n: 0 for n in self.flat.names}          # per-parameter step count (torch keeps one per parameter)
@@ -139,10 +153,21 @@ class FusedAdam:
     def step(self, grad_scale=1.0):
         self.flat.check_links()
         runs = self._runs()
+        if self.max_grad_norm is not None and runs:
+            if self.grad_stats is None:
+                from .tensor_stats import TensorStats
+                self.grad_stats = TensorStats(self.flat, bins=1)
+            out = self.grad_stats.run(self.flat.grads, names=[n for r in runs for n in r[3]], hist=False,
+                                      max_norm=self.max_grad_norm, grad_scale=grad_scale)
+            self.grad_norm, self.clip_scale = out["norm"], out["scale"]
         for lo, hi, st, _ in runs:
             hi = min(hi, self.flat.total)
-            ops.adam_step(self.flat.params[lo:hi], self.flat.grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                          self.lr, st, self.betas, self.eps, grad_scale)
+            if self.max_grad_norm is not None:
+                ops.adam_step_dscale(self.flat.params[lo:hi], self.flat.grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                     self.lr, st, self.clip_scale, self.betas, self.eps)
+            else:
+                ops.adam_step(self.flat.params[lo:hi], self.flat.grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                              self.lr, st, self.betas, self.eps, grad_scale)
         self._commit(runs)
 
     def zero_grad(self, set_to_none=False):
@@ -336,10 +361,13 @@ class TrainStep:
     """One optimizer step of the fusion network, autograd-free (see module docstring)."""
 
     def __init__(self, model, lr=1e-5, loss_coeff=0.001, num_seq=1, betas=(0.9, 0.999), eps=1e-8,
-                 process_group=None, sync_bn=False, grad_wire_dtype=None):
+                 process_group=None, sync_bn=False, grad_wire_dtype=None, max_grad_norm=None):
+        """`max_grad_norm`: FusedAdam's gradient-norm clipping.  It runs once per optimizer step, in the `last` window after the
+        all-reduce has finished, on the accumulated, summed gradient times 1 / world -- the norm of the AVERAGED gradient, as DDP
+        followed by clip_grad_norm_ gives; every rank computes it from identical bytes, so there is no extra collective."""
         self.model = model
         self.flat = FlatParams(model)
-        self.opt = FusedAdam(self.flat, lr, betas, eps)
+        self.opt = FusedAdam(self.flat, lr, betas, eps, max_grad_norm=max_grad_norm)
         self.loss_coeff, self.num_seq = loss_coeff, num_seq
         self.sync = GradSync(self.flat.grads, self.flat.fusion_end, process_group, flat=self.flat, wire_dtype=grad_wire_dtype)
         # replicas start identical: rank 0's weights (one flat buffer) and BatchNorm buffers, like DDP's constructor
