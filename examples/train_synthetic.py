@@ -11,6 +11,7 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --raw_audio [--compress_audio]         # 44.1 kHz stereo int16 clips through AudioTransform first
     python examples/train_synthetic.py --mix 2 --mix_snr 0 10                 # mix-and-separate: every clip + 2 others of the batch at 0..10 dB
     python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
+    python examples/train_synthetic.py --val 2                                # every 2 steps: held-out loss and LSD, a checkpoint on improvement
 """
 import argparse
 import os
@@ -49,6 +50,9 @@ def main():
                     help="clip the global gradient norm (clip_grad_norm_'s rule, on the device: TrainStep(max_grad_norm=...))")
     ap.add_argument("--watch", type=int, default=0, metavar="N",
                     help="every N steps, the per-tensor gradient / parameter histograms wandb.watch would log (maavss_amd.ModelWatch)")
+    ap.add_argument("--val", type=int, default=0, metavar="N",
+                    help="every N steps, validate on one fixed seeded held-out batch (maavss_amd.Validator: train_av_net.py:147-181) and "
+                         "save a checkpoint when the validation loss improves")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
@@ -99,6 +103,16 @@ def main():
 
     fixed = batch() if a.overfit else None
     sr_arg = dict(audio_sr=raw_sr) if a.raw_audio else {}
+    held_out = validator = val_dir = None
+    if a.val:
+        # one held-out batch from a generator of its own (the training stream's draws stay what they are without --val), extracted once
+        g_train, g = g, torch.Generator().manual_seed(12345)
+        pipe.submit(*batch(), seed=12345, **sr_arg)
+        held_out = tuple(t.clone() for t in pipe.get())
+        pipe.release()
+        g = g_train
+        validator = maavss_amd.Validator(model, loss_coeff=0.001, num_seq=ns)
+        val_dir = tempfile.TemporaryDirectory()
     pipe.submit(*(fixed or batch()), seed=0, **sr_arg)
     for i in range(a.steps):
         pipe.submit(*(fixed or batch()), seed=0 if a.overfit else i + 1, **sr_arg)      # extraction of the next batch: side stream
@@ -109,6 +123,17 @@ def main():
         if i % a.log_every == 0 or i == a.steps - 1:
             clip = "" if a.clip is None else f"  |g| {step.opt.grad_norm.item():.4g}  scale {step.opt.clip_scale.item():.4g}"
             print(f"step {i}: a_loss {losses[0].item():.5f}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}", flush=True)
+        if validator is not None and (i + 1) % a.val == 0:
+            attn_v, x_v_stft, y_v_stft = held_out
+            model.eval()
+            validator.reset()
+            validator.add_clips(x_v_stft, y_v_stft, attn_v, attn_v, nf, hpf)
+            res = validator.result()
+            model.train()
+            print(f"step {i}: validation {res}", flush=True)
+            if validator.improved(res):
+                maavss_amd.save_checkpoint(model.state_dict(), step.opt.state_dict(), i, res["val_loss"], "synthetic-best", val_dir.name)
+                print(f"step {i}: val_loss {res['val_loss']:.5f} improved: checkpoint saved", flush=True)
         if logs is not None:
             # with wandb: wandb.log({k: wandb.Histogram(np_histogram=v) for k, v in logs.items() if not k.startswith("nonfinite/")})
             bad = [k for k in logs if k.startswith("nonfinite/")]
@@ -116,6 +141,8 @@ def main():
             print(f"step {i}: {len(logs) - len(bad)} histograms; gradients/fc2.weight in [{edges[0]:.3g}, {edges[-1]:.3g}], fullest bin "
                   f"{int(counts.argmax())} of {len(counts)}; tensors with non-finite values: {len(bad)}", flush=True)
     pipe.drain()
+    if val_dir is not None:
+        val_dir.cleanup()
 
     with tempfile.TemporaryDirectory() as cp_dir:
         maavss_amd.save_checkpoint(model.state_dict(), step.opt.state_dict(), 0, losses[2].item(), "synthetic", cp_dir)

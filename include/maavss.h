@@ -331,6 +331,51 @@ int maavss_tensor_stats(const float* buf, int64_t n, const int64_t* chunks, int6
                         double* sumsq, float* seg_min, float* seg_max, int* nonfinite, int* hist, int bins, double max_norm,
                         float grad_scale, double* total_sumsq, float* norm, float* scale, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- EXTENSION: quality metrics of held-out data (maavss_amd.quality: wave_metrics, spectrum_metrics, Validator) ---------------
+ * The reference validates: train_avse_frames.py:55-65 splits off a validation set, train_av_net.py:147-181 averages the loss over
+ * val_steps batches under model.eval() + torch.no_grad() and saves a checkpoint when it improves (:174-181).  These entry points are the
+ * reductions of that pass, plus the waveform measures an enhanced recording is judged by.  Added without a version bump.  Every sum is
+ * f64 over the f32 inputs, in a fixed order (partials in the workspace, combined in index order): no floating-point atomics, two runs
+ * give identical bytes.  No epsilon anywhere.
+ *
+ * maavss_wave_metrics: per row of est [B][L] against ref [B][L]; strides in elements, >= 0, rows may overlap (stride < L), ignored when
+ * B = 1; the pointers need 4-byte alignment only.  out [B][9] f64:
+ *   0 Sxx = sum ref^2   1 Syy = sum est^2   2 Sxy = sum ref est   3 See = sum (est - ref)^2
+ *   4 Srr = sum (est - alpha ref)^2, alpha = Sxy / Sxx, summed directly in a second pass over the rows
+ *   5 snr_db = 10 log10(Sxx / See) (+inf when est == ref; NaN when Sxx = 0: without a reference there is no ratio)
+ *   6 si_sdr_db = 10 log10(alpha^2 Sxx / Srr) (+inf when est = c ref, -inf when Sxy = 0, NaN when Sxx = 0)
+ *   7 seg_snr_db = mean over the floor(L / seg_len) complete frames with Sxx_f > 0 of clamp(10 log10(Sxx_f / See_f), -10, 35); a trailing
+ *     partial frame is dropped; NaN when no frame counts      8 the number of frames that counted
+ * A non-finite sample in est or ref makes columns 0-7 of that row NaN and column 8 zero.  1 <= seg_len <= CH = maavss_wave_metrics_chunk():
+ * a row is cut into ceil(L / CL) chunks of CL = floor(CH / seg_len) * seg_len samples (whole frames; the last chunk takes the rest), one
+ * workgroup each, so a single long row uses the whole device.  ws: maavss_wave_metrics_ws_bytes(B, L, seg_len) bytes, 8-byte aligned =
+ * round256(48 * B * chunks) [{Sxx, Syy, Sxy, See, frame sum, frame count} per chunk] + round256(8 * B * chunks) [Srr] + round256(8 * B)
+ * [alpha]; 0 for invalid arguments.  Four launches: pass 1, finalize, pass 2, finalize. */
+int maavss_wave_metrics_chunk(void);
+int64_t maavss_wave_metrics_ws_bytes(int64_t B, int64_t L, int seg_len);
+int maavss_wave_metrics(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L, int seg_len,
+                        double* out, void* ws, int64_t ws_bytes, void* stream);
+/* maavss_spectrum_metrics: per row of pred [B][2][T][F] against tgt (contiguous; F may be odd).  out [B][2] f64:
+ *   0 the squared-error sum over the 2 T F elements -- the numerator of the reference's MSE (train_avse_frames.py:166)
+ *   1 lsd_db = mean over T of sqrt(mean over F of (10 log10(max(P_pred, floor)) - 10 log10(max(P_tgt, floor)))^2), P = re^2 + im^2 in f64;
+ *     lsd_floor > 0 is a power.  A NaN power stays a NaN.
+ * ws: maavss_spectrum_metrics_ws_bytes(B, T) = round256(16 * B * T) bytes [{squared error, frame distance} per (b, t)].
+ * maavss_sqerr_rows: out [B] f64 = sum over n of (pred - tgt)^2 per row of two contiguous [B][n] arrays (the attention term of the loss,
+ * train_avse_frames.py:167); ws: maavss_sqerr_rows_ws_bytes(B, n) = round256(8 * B * ceil(n / maavss_sqerr_rows_chunk())) bytes. */
+int64_t maavss_spectrum_metrics_ws_bytes(int64_t B, int64_t T);
+int maavss_spectrum_metrics(const float* pred, const float* tgt, int64_t B, int64_t T, int64_t F, double lsd_floor, double* out, void* ws,
+                            int64_t ws_bytes, void* stream);
+int maavss_sqerr_rows_chunk(void);
+int64_t maavss_sqerr_rows_ws_bytes(int64_t B, int64_t n);
+int maavss_sqerr_rows(const float* pred, const float* tgt, int64_t B, int64_t n, double* out, void* ws, int64_t ws_bytes, void* stream);
+/* The Validator's additive f64 accumulator (sums and counts only: the mean over val_steps batches of train_av_net.py:160-172 is a
+ * quotient taken on the host at the end), updated on the device, one wave, fixed order.
+ * add_sum: acc[0] += sum_i vals[i * stride], acc[1] += n * weight (the number of elements behind the n values).
+ * add_classes: for each column c < cols, v_i = vals[i * stride + c] - minus[i * stride + c] (minus nullable: v_i = vals[...]);
+ * acc[5 c + 0..4] += {sum of the finite v_i, count of finite, +inf, -inf, NaN}. */
+int maavss_metric_add_sum(const double* vals, int64_t n, int64_t stride, double weight, double* acc, void* stream);
+int maavss_metric_add_classes(const double* vals, const double* minus, int64_t n, int64_t stride, int cols, double* acc, void* stream);
+
 /* K18 helper, EXTENSION (the reference is single-device): bf16 wire format of the data-parallel gradient all-reduce -- a bucket of
  * the flat f32 gradient buffer is rounded to bf16 (round-to-nearest-even) for the collective and widened back into the f32 master
  * buffer afterwards (trainer.GradSync(wire_dtype="bf16")).  n a multiple of 8, buffers 16-byte aligned. */

@@ -1,0 +1,270 @@
+"""Validation on the device: held-out loss and per-clip quality metrics of waveforms and spectra.
+
+The reference validates (train_avse_frames.py:55-65 splits off a validation set; train_av_net.py:147-181 runs `model.eval()` +
+`torch.no_grad()` over `val_steps` batches, averages the loss and saves a checkpoint only when it improves).  `TrainStep` is
+autograd-free and always trains; this module is the loss-only path next to it, and the measures an `Enhancer` output or a `Mixer`
+example is judged by (csrc/quality_metrics.hip: f64 sums of the f32 data in a fixed order, no floating-point atomics).
+
+* `plan_wave_chunks` -- the host-side chunk planner of the wave metrics (pure, no device)
+* `wave_metrics`     -- per row of est [B, L] against ref [B, L]: Sxx, Syy, Sxy, See, Srr, SNR, SI-SDR, segmental SNR
+* `spectrum_metrics` -- per row of pred [B, 2, T, F] against tgt: squared-error sum and log-spectral distance
+* `Validator`        -- an additive device accumulator of both over batches, clips and recordings; `result()` makes the one copy
+
+Definitions (include/maavss.h states them next to the entry points; tests/quality_twin.py is their float64 restatement):
+  snr_db = 10 log10(Sxx / See), si_sdr_db = 10 log10(alpha^2 Sxx / Srr) with alpha = Sxy / Sxx and Srr = sum (est - alpha ref)^2 summed
+  directly, seg_snr_db = the mean over the complete frames of seg_len samples whose reference is not silent of the frame's SNR clamped
+  to [-10, 35] dB.  No epsilon: est == ref gives +inf, a silent reference NaN, a non-finite sample makes its row NaN.
+Nothing here synchronises with the host before `Validator.result()`.
+"""
+import torch
+
+from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr
+from .trainer import sliding_windows
+
+WAVE_COLUMNS = ("sxx", "syy", "sxy", "see", "srr", "snr_db", "si_sdr_db", "seg_snr_db", "n_frames")
+WAVE_DB = ("snr_db", "si_sdr_db", "seg_snr_db")            # columns 5..7 of a wave_metrics row
+_DB0 = WAVE_COLUMNS.index("snr_db")
+
+
+def wave_chunk():
+    """CH: the most samples one workgroup of the wave metrics reduces (a constant of the library); seg_len may not exceed it."""
+    return int(query("maavss_wave_metrics_chunk"))
+
+
+def plan_wave_chunks(length, seg_len, ch):
+    """[(start, n)]: one row of `length` samples cut into chunks of floor(ch / seg_len) * seg_len samples -- a whole number of frames of
+    seg_len samples each, so that no frame of the segmental SNR is split; the last chunk takes what is left, the row's trailing partial
+    frame included.  Every sample is in exactly one chunk.  The library cuts every row the same way (one workgroup per chunk)."""
+    length, seg_len, ch = int(length), int(seg_len), int(ch)
+    if length < 1:
+        raise ValueError("length must be >= 1")
+    if not 1 <= seg_len <= ch:
+        raise ValueError(f"seg_len must be in 1..{ch} (the chunk length), got {seg_len}")
+    cl = ch // seg_len * seg_len
+    return [(a, min(cl, length - a)) for a in range(0, length, cl)]
+
+
+def _rows(t, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (1, 2):
+        raise ValueError(f"{what} must be a float32 tensor [L] or [B, L], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+    t = t[None] if t.dim() == 1 else t
+    if t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{what} is empty: {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < 0:
+        t = t.contiguous()
+    return t
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 8) // 8, dtype=torch.float64, device=dev)
+
+
+def wave_metrics(est, ref, seg_len=256):
+    """est, ref: f32 cuda [L] or [B, L], samples contiguous, any row stride >= 0 (rows may overlap) and any 4-byte-aligned offset -- a slice
+    `clean[start:start + n]` is taken as it is.  -> dict of device f64 tensors [B]: sxx, syy, sxy, see, srr, snr_db, si_sdr_db, seg_snr_db,
+    n_frames, and "raw" [B, 9], the one buffer they are columns of.  Only enqueues launches on the current stream."""
+    est, ref = _rows(est, "est"), _rows(ref, "ref")
+    if est.shape != ref.shape:
+        raise ValueError(f"est {tuple(est.shape)} and ref {tuple(ref.shape)} differ in shape")
+    ch = wave_chunk()
+    if not 1 <= int(seg_len) <= ch:
+        raise ValueError(f"seg_len must be in 1..{ch}, got {seg_len}")
+    require_cuda(est, ref)
+    b, n = est.shape
+    out = torch.empty(b, len(WAVE_COLUMNS), dtype=torch.float64, device=est.device)
+    nbytes = int(query("maavss_wave_metrics_ws_bytes", b, n, int(seg_len)))
+    ws = _ws(nbytes, est.device)
+    call("maavss_wave_metrics", ptr(est), est.stride(0), ptr(ref), ref.stride(0), b, n, int(seg_len), ptr(out), ptr(ws), nbytes, stream_ptr())
+    res = {k: out[:, i] for i, k in enumerate(WAVE_COLUMNS)}
+    res["raw"] = out
+    return res
+
+
+def spectrum_metrics(pred, tgt, lsd_floor=1e-10):
+    """pred, tgt: f32 cuda [B, 2, T, F] (real and imaginary planes, as the model's audio output and its target) -> dict of device f64
+    tensors [B]: sqerr (sum of the squared differences over the 2 T F elements: the numerator of the MSE) and lsd_db (log-spectral distance
+    in dB over the powers re^2 + im^2, floored at `lsd_floor`), and "raw" [B, 2]."""
+    for t, what in ((pred, "pred"), (tgt, "tgt")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 2 or t.numel() == 0:
+            raise ValueError(f"{what} must be a non-empty float32 tensor [B, 2, T, F], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+    if pred.shape != tgt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and tgt {tuple(tgt.shape)} differ in shape")
+    if not float(lsd_floor) > 0.0:
+        raise ValueError("lsd_floor must be > 0 (a power)")
+    require_cuda(pred, tgt)
+    pred, tgt = pred.contiguous(), tgt.contiguous()
+    b, _, t, f = pred.shape
+    out = torch.empty(b, 2, dtype=torch.float64, device=pred.device)
+    nbytes = int(query("maavss_spectrum_metrics_ws_bytes", b, t))
+    ws = _ws(nbytes, pred.device)
+    call("maavss_spectrum_metrics", ptr(pred), ptr(tgt), b, t, f, float(lsd_floor), ptr(out), ptr(ws), nbytes, stream_ptr())
+    return {"sqerr": out[:, 0], "lsd_db": out[:, 1], "raw": out}
+
+
+def sqerr_rows(pred, tgt):
+    """pred, tgt: f32 cuda, same shape [B, ...] -> device f64 [B]: the sum of the squared differences per batch row (the attention term)."""
+    if pred.shape != tgt.shape or pred.dtype != torch.float32 or tgt.dtype != torch.float32 or pred.dim() < 1 or pred.numel() == 0:
+        raise ValueError(f"pred and tgt must be non-empty float32 tensors of one shape, got {tuple(pred.shape)} and {tuple(tgt.shape)}")
+    require_cuda(pred, tgt)
+    pred, tgt = pred.contiguous(), tgt.contiguous()
+    b = pred.shape[0]
+    n = pred.numel() // b
+    out = torch.empty(b, dtype=torch.float64, device=pred.device)
+    nbytes = int(query("maavss_sqerr_rows_ws_bytes", b, n))
+    ws = _ws(nbytes, pred.device)
+    call("maavss_sqerr_rows", ptr(pred), ptr(tgt), b, n, ptr(out), ptr(ws), nbytes, stream_ptr())
+    return out
+
+
+# the accumulator: [stft sqerr, stft elements, lsd sum, windows, attn sqerr, attn elements], then five numbers {sum of the finite values,
+# count finite, +inf, -inf, NaN} for each wave metric of the estimates, of the noisy inputs, and of estimate minus noisy per clip
+_SUMS = ("stft", "lsd", "attn")
+_GROUPS = ("est", "noisy", "gain")
+_ACC_LEN = 2 * len(_SUMS) + 5 * len(WAVE_DB) * len(_GROUPS)
+
+
+class Validator:
+    """Held-out loss and quality metrics, accumulated on the device.
+
+        val = maavss_amd.Validator(model, loss_coeff=0.001, num_seq=3)
+        model.eval()
+        val.reset()
+        for x_stft, y_stft, attn in held_out:
+            val.add_clips(x_stft, y_stft, attn, attn, num_frames, hops_per_frame)
+        val.add_recording(enhancer, noisy, clean, attn=maps)
+        res = val.result()                      # the one device-to-host copy
+        if val.improved(res):
+            save_checkpoint(...)                # train_av_net.py:174-181
+        model.train()
+
+    The accumulator is one small f64 device tensor (`.acc`) of sums and counts only, so it is additive: the element-wise sum of the
+    accumulators of several ranks is the accumulator of their data.  `add_*` enqueue kernels on the current stream and never wait."""
+
+    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10):
+        if int(num_seq) < 1:
+            raise ValueError("num_seq must be >= 1")
+        if int(seg_len) < 1:
+            raise ValueError("seg_len must be >= 1")
+        if not float(lsd_floor) > 0.0:
+            raise ValueError("lsd_floor must be > 0 (a power)")
+        self.model, self.loss_coeff, self.num_seq = model, float(loss_coeff), int(num_seq)
+        self.seg_len, self.lsd_floor = int(seg_len), float(lsd_floor)
+        self.acc = None
+        self.best = None
+
+    def reset(self):
+        """Clear the accumulator (the best val_loss `improved` keeps is not touched)."""
+        if self.acc is not None:
+            self.acc.zero_()
+
+    def _acc(self, dev):
+        if self.acc is None:
+            self.acc = torch.zeros(_ACC_LEN, dtype=torch.float64, device=dev)
+        return self.acc
+
+    def _slot(self, kind, group=None):
+        if group is None:
+            o = 2 * _SUMS.index(kind)
+            return self.acc[o:o + 2]
+        o = 2 * len(_SUMS) + 5 * len(WAVE_DB) * _GROUPS.index(group)
+        return self.acc[o:o + 5 * len(WAVE_DB)]
+
+    def _check_eval(self):
+        if self.model.training:
+            raise ValueError("the model is in training mode: call model.eval() first (train_av_net.py:147); a validation pass must "
+                             "not update the BatchNorm running statistics")
+
+    def add_windows(self, x_a, x_v, y_a, y_v):
+        """One batch of windows: x_a [B,2,T_a,F], x_v [B,1,T,H,W] and the targets y_a [B,2,a,F], y_v [B,1,H,W] as TrainStep takes them.
+        Forward only (the public eval forward under no_grad: no gradient buffer is written, BatchNorm reads its running statistics)."""
+        self._check_eval()
+        require_cuda(x_a, x_v, y_a, y_v)
+        with torch.no_grad():
+            a, v, _ = self.model(x_a, x_v)
+        if a.shape != y_a.shape or v.shape != y_v.shape:
+            raise ValueError(f"targets {tuple(y_a.shape)}, {tuple(y_v.shape)} do not match the model's outputs {tuple(a.shape)}, {tuple(v.shape)}")
+        self._acc(a.device)
+        st = stream_ptr()
+        spec = spectrum_metrics(a, y_a, self.lsd_floor)["raw"]
+        b = spec.shape[0]
+        call("maavss_metric_add_sum", ptr(spec), b, 2, float(a.numel() // b), ptr(self._slot("stft")), st)
+        call("maavss_metric_add_sum", ptr(spec[:, 1]), b, 2, 1.0, ptr(self._slot("lsd")), st)
+        attn = sqerr_rows(v, y_v)
+        call("maavss_metric_add_sum", ptr(attn), b, 1, float(v.numel() // b), ptr(self._slot("attn")), st)
+
+    def add_clips(self, x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame):
+        """One batch of clips, cut into the `num_seq` windows TrainStep.sliding_window_step trains on (the same slicing code)."""
+        self._check_eval()
+        for _, xa, xv, ya, yv in sliding_windows(x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, self.num_seq):
+            self.add_windows(xa, xv, ya, yv)
+
+    def add_waves(self, est, ref, noisy=None):
+        """Per-row wave metrics of est against ref, each row one clip; with `noisy` (the unprocessed input of the same rows) also its own
+        metrics against ref and, per clip, estimate minus noisy: the improvements (SNRi, SI-SDRi, segmental SNRi)."""
+        m = wave_metrics(est, ref, self.seg_len)["raw"]
+        self._acc(m.device)
+        st = stream_ptr()
+        b, cols, k = m.shape[0], m.shape[1], len(WAVE_DB)
+        call("maavss_metric_add_classes", ptr(m[:, _DB0:]), None, b, cols, k, ptr(self._slot(None, "est")), st)
+        if noisy is not None:
+            mn = wave_metrics(noisy, ref, self.seg_len)["raw"]
+            if mn.shape != m.shape:
+                raise ValueError("noisy must have the shape of est")
+            call("maavss_metric_add_classes", ptr(mn[:, _DB0:]), None, b, cols, k, ptr(self._slot(None, "noisy")), st)
+            call("maavss_metric_add_classes", ptr(m[:, _DB0:]), ptr(mn[:, _DB0:]), b, cols, k, ptr(self._slot(None, "gain")), st)
+
+    def add_recording(self, enhancer, noisy, clean, frames=None, attn=None):
+        """Enhance `noisy` [L] with `enhancer(noisy, frames= | attn=)` -> (wave, start) and measure the estimate and the noisy input against
+        clean[start : start + len(wave)], the span the estimate covers."""
+        self._check_eval()
+        if enhancer.model is not self.model:
+            raise ValueError("the Enhancer wraps another model than this Validator")
+        if not isinstance(clean, torch.Tensor) or clean.dim() != 1 or clean.dtype != torch.float32:
+            raise ValueError(f"clean must be a 1-D float32 tensor, got {getattr(clean, 'shape', type(clean))}")
+        require_cuda(noisy, clean)
+        wave, start = enhancer(noisy, frames=frames, attn=attn)
+        n = wave.shape[0]
+        if clean.shape[0] < start + n:
+            raise ValueError(f"clean has {clean.shape[0]} samples, the estimate covers [{start}, {start + n})")
+        self.add_waves(wave, clean[start:start + n], noisy=noisy[start:start + n])
+
+    def result(self):
+        """The one device-to-host copy (it waits for the stream) -> dict:
+        val_loss_stft, val_loss_attn (total squared error over total elements: a ragged last batch is weighted by its size), val_loss =
+        stft + loss_coeff * attn, lsd_db (mean over windows), n_windows; per wave metric m in snr_db, si_sdr_db, seg_snr_db: m (the mean
+        over the clips whose value is finite) and m_n_finite / _n_posinf / _n_neginf / _n_nan; with noisy inputs also noisy_m (and its
+        counts) and m_improvement = the mean over clips of estimate minus noisy; n_clips.  A quantity nothing was added to is NaN."""
+        nan = float("nan")
+        if self.acc is None:
+            h = [0.0] * _ACC_LEN
+        else:
+            h = self.acc.cpu().tolist()
+
+        def ratio(s, n):
+            return s / n if n > 0 else nan
+
+        out = {"val_loss_stft": ratio(h[0], h[1]), "lsd_db": ratio(h[2], h[3]), "val_loss_attn": ratio(h[4], h[5]), "n_windows": int(h[3])}
+        out["val_loss"] = out["val_loss_stft"] + self.loss_coeff * out["val_loss_attn"]
+        o = 2 * len(_SUMS)
+        for group in _GROUPS:
+            for name in WAVE_DB:
+                s, nf, npos, nneg, nnan = h[o:o + 5]
+                o += 5
+                total = int(nf + npos + nneg + nnan)
+                if group == "est":
+                    out["n_clips"] = total
+                elif total == 0:
+                    continue
+                key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
+                out[key] = ratio(s, nf)
+                out.update({f"{key}_n_finite": int(nf), f"{key}_n_posinf": int(npos), f"{key}_n_neginf": int(nneg), f"{key}_n_nan": int(nnan)})
+        return out
+
+    def improved(self, result):
+        """True when result["val_loss"] is lower than every one seen before (and keeps it in `.best`): the reference's "save on
+        improvement" (train_av_net.py:174-181).  A NaN loss never improves."""
+        loss = float(result["val_loss"])
+        if loss == loss and (self.best is None or loss < self.best):
+            self.best = loss
+            return True
+        return False

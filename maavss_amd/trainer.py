@@ -357,6 +357,22 @@ def shard_batch(global_batch, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def sliding_windows(x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, num_seq):
+    """The reference's window slicing (train_avse_frames.py:143-163) as views, shared by TrainStep.sliding_window_step and
+    quality.Validator.add_clips: yields (j, x_a, x_v, y_a, y_v) for j < num_seq -- frames [j, j + num_frames) of x_attn [B,1,T,H,W] with
+    the matching STFT frames of x_stft [B,2,T_a,F]; the targets are attention frame j + idx_mid of y_attn and the STFT frames of that
+    video frame of y_stft, idx_mid = (num_seq - 1) // 2 (:105)."""
+    hpf, ns = hops_per_frame, num_seq
+    mid = (ns - 1) // 2
+    assert x_attn.shape[2] >= num_frames + ns - 1 and x_stft.shape[2] >= hpf * (num_frames + ns - 1)
+    for j in range(ns):
+        xa = x_stft[:, :, hpf * j:hpf * (j + num_frames), :]
+        ya = y_stft[:, :, hpf * (j + mid):hpf * (j + mid + 1), :]
+        xv = x_attn[:, :, j:j + num_frames]
+        yv = y_attn[:, :, j + mid]
+        yield j, xa, xv, ya, yv
+
+
 class TrainStep:
     """One optimizer step of the fusion network, autograd-free (see module docstring)."""
 
@@ -408,15 +424,9 @@ class TrainStep:
         (accumulated in the flat buffer); ONE gradient all-reduce and ONE Adam step follow.  Returns the last
         window's (a_loss, v_loss, loss) like the reference logs (:183-188) and, with `collect`, the stitched
         outputs (output_stft [B,2,hpf*num_seq,F], output_attn [B,1,num_seq,H,W]) of its callback (:150-176)."""
-        hpf, ns = hops_per_frame, self.num_seq
-        mid = (ns - 1) // 2
-        assert x_attn.shape[2] >= num_frames + ns - 1 and x_stft.shape[2] >= hpf * (num_frames + ns - 1)
+        ns = self.num_seq
         outs_a, outs_v = [], []
-        for j in range(ns):
-            xa = x_stft[:, :, hpf * j:hpf * (j + num_frames), :]
-            ya = y_stft[:, :, hpf * (j + mid):hpf * (j + mid + 1), :]
-            xv = x_attn[:, :, j:j + num_frames]
-            yv = y_attn[:, :, j + mid]
+        for j, xa, xv, ya, yv in sliding_windows(x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, ns):
             self(xa, xv, ya, yv, accumulate=j > 0, last=j == ns - 1)
             if collect:
                 outs_a.append(self.outputs[0])
