@@ -142,6 +142,12 @@ def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+def workspace(nbytes, device):
+    """Uninitialised device scratch of at least `nbytes` bytes (what a `*_ws_bytes` query returned), 8-byte aligned as the entry points ask."""
+    import torch
+    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.float64, device=device)
+
+
 def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

@@ -57,14 +57,9 @@ __global__ __launch_bounds__(1024) void audio_transform_absmax_kernel(const T* _
   const float fC = (float)C;
   float m = 0.f;
   for (int64_t g = threadIdx.x; g < L0; g += 1024) m = fmaxf(m, fabsf(at_downmix(clip, stride_c, C, fC, g)));
-  m = wave_max(m);
-  __shared__ float red[16];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int q = 1; q < 16; ++q) m = fmaxf(m, red[q]);
-    scale[blockIdx.x] = m;
-  }
+  __shared__ float red[16][1];
+  m = wg_reduce<WG_THREAD0, WG_MAX>(wave_max(m), red, threadIdx.x >> 6, threadIdx.x & 63);
+  if (threadIdx.x == 0) scale[blockIdx.x] = m;
 }
 
 // grid (blocks_per_clip * B), block AT_RUN, dynamic LDS span * 4 bytes (RESAMPLE only)
@@ -143,7 +138,7 @@ int at_launch(const T* src, int64_t B, int C, int64_t L0, int64_t stride_b, int6
 
 extern "C" int64_t maavss_audio_transform_ws_bytes(int64_t B, int C, int64_t L0, int normalize) {
   if (!at_shape_ok(B, C, L0)) return -1;
-  return normalize ? ((B * 4 + 255) & ~(int64_t)255) : 0;
+  return normalize ? align256(B * 4) : 0;
 }
 
 extern "C" int maavss_audio_transform(const void* src, int src_dtype, int64_t B, int C, int64_t L0, int64_t stride_b, int64_t stride_c,

@@ -28,7 +28,7 @@ __device__ __forceinline__ int64_t av_clip_first_frame(const int32_t* clip_start
 __global__ __launch_bounds__(256) void av_clip_scale_kernel(const float* __restrict__ maps, const float* __restrict__ fmax,
                                                             const int32_t* __restrict__ clip_start, int64_t n_frames, int clip_frames,
                                                             int64_t frame_elems, int attn_diff, float* __restrict__ clip_rcp) {
-  __shared__ float red[4];
+  __shared__ float red[4][1];
   const int64_t c = blockIdx.x;
   const int64_t f0 = av_clip_first_frame(clip_start, c, n_frames, clip_frames);
   const float* mp = maps + f0 * frame_elems;
@@ -45,10 +45,8 @@ __global__ __launch_bounds__(256) void av_clip_scale_kernel(const float* __restr
     const int64_t n = (int64_t)clip_frames * frame_elems;
     for (int64_t e = threadIdx.x; e < n; e += 256) mx = fmaxf(mx, mp[e]);
   }
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) clip_rcp[c] = 1.f / fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  mx = wg_reduce<WG_THREAD0, WG_MAX>(wave_max(mx), red, threadIdx.x >> 6, threadIdx.x & 63);
+  if (threadIdx.x == 0) clip_rcp[c] = 1.f / mx;
 }
 
 __global__ __launch_bounds__(256) void av_attn_windows_kernel(const float* __restrict__ maps, const float* __restrict__ clip_rcp,

@@ -10,7 +10,8 @@
 //   pass 2      the same chunks again: Srr = sum (est - alpha ref)^2, summed directly (Syy - Sxy^2 / Sxx cancels at high quality)
 //   finalize 2  Srr and si_sdr_db
 // Spectrum metrics of pred [B][2][T][F] against tgt: one wave per (b, t) frame -> {squared error, sqrt(mean_F d^2)}, one wave per row
-// adds the T frames in order.  The plain squared-error rows (the attention term) are the same two steps over chunks of SQ_CH elements.
+// adds the T frames in order.  The plain squared-error rows (the attention term) are pass 2's kernel with alpha = 1 over chunks of SQ_CH
+// elements, then that row sum.  The wave and workgroup orders are those of reduce.h.
 // No floating-point atomic anywhere: every output has the same bits in every run.  A product that is not exact is rounded before it is
 // added, so the terms are the ones tests/quality_twin.py sums and only the order of the additions differs: the Makefile compiles this
 // file with -ffp-contract=off (under the library's -ffp-contract=fast the backend fuses across `#pragma clang fp contract(off)`); the
@@ -27,7 +28,6 @@ struct wm_partial {
 };
 static_assert(sizeof(wm_partial) == 48, "workspace layout of include/maavss.h");
 
-static inline int64_t qm_align256(int64_t b) { return (b + 255) / 256 * 256; }
 static inline int wm_chunk_len(int seg_len) { return WM_CH / seg_len * seg_len; }
 static inline int64_t wm_chunks_per_row(int64_t L, int seg_len) { return (L + wm_chunk_len(seg_len) - 1) / wm_chunk_len(seg_len); }
 
@@ -37,13 +37,6 @@ __device__ __forceinline__ double qm_nan() { return __longlong_as_double(0x7ff80
 __device__ __forceinline__ double qm_group_sum(double v, int G) {
   for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// sum of p[0], p[stride], ..., p[(count - 1) * stride] by one wave, in a fixed order: lane l adds elements l, l + 64, ..., then the butterfly
-__device__ __forceinline__ double qm_wave_strided_sum(const double* __restrict__ p, int64_t count, int64_t stride, int lane) {
-  double s = 0.0;
-  for (int64_t i = lane; i < count; i += 64) s += p[i * stride];
-  return wave_sum_d(s);
 }
 
 // G lanes per frame (the smallest power of two >= seg_len, at most 64): 256 / G frames per step of the workgroup.  A lane keeps the
@@ -99,31 +92,12 @@ __global__ __launch_bounds__(256) void wave_metrics_pass1_kernel(const float* __
       pend = false;
     }
   }
-  tx = wave_sum_d(tx);
-  ty = wave_sum_d(ty);
-  txy = wave_sum_d(txy);
-  te = wave_sum_d(te);
-  seg = wave_sum_d(seg);
-  frames = wave_sum_d(frames);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) {
-    red[w][0] = tx;
-    red[w][1] = ty;
-    red[w][2] = txy;
-    red[w][3] = te;
-    red[w][4] = seg;
-    red[w][5] = frames;
-  }
-  __syncthreads();
+  double v[6] = {wave_sum_d(tx), wave_sum_d(ty), wave_sum_d(txy), wave_sum_d(te), wave_sum_d(seg), wave_sum_d(frames)};
+  wg_reduce<WG_THREAD0, WG_SUM>(v, red, tid >> 6, tid & 63);
   if (tid == 0) {
-    wm_partial p;
-    p.sxx = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    p.syy = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    p.sxy = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
-    p.see = (red[0][3] + red[1][3]) + (red[2][3] + red[3][3]);
-    p.seg = (red[0][4] + red[1][4]) + (red[2][4] + red[3][4]);
-    p.frames = (red[0][5] + red[1][5]) + (red[2][5] + red[3][5]);
-    partials[blockIdx.x] = p;
+    double* __restrict__ p = reinterpret_cast<double*>(partials + blockIdx.x);      // sxx, syy, sxy, see, seg, frames
+#pragma unroll
+    for (int k = 0; k < 6; ++k) p[k] = v[k];
   }
 }
 
@@ -133,9 +107,9 @@ __global__ __launch_bounds__(64) void wave_metrics_finalize1_kernel(const wm_par
   const int64_t row = blockIdx.x;
   const int lane = threadIdx.x;
   const double* __restrict__ p = reinterpret_cast<const double*>(partials + row * nch);
-  const double sxx = qm_wave_strided_sum(p + 0, nch, 6, lane), syy = qm_wave_strided_sum(p + 1, nch, 6, lane);
-  const double sxy = qm_wave_strided_sum(p + 2, nch, 6, lane), see = qm_wave_strided_sum(p + 3, nch, 6, lane);
-  const double seg = qm_wave_strided_sum(p + 4, nch, 6, lane), frames = qm_wave_strided_sum(p + 5, nch, 6, lane);
+  const double sxx = wave_strided_sum_d(p + 0, nch, 6, lane), syy = wave_strided_sum_d(p + 1, nch, 6, lane);
+  const double sxy = wave_strided_sum_d(p + 2, nch, 6, lane), see = wave_strided_sum_d(p + 3, nch, 6, lane);
+  const double seg = wave_strided_sum_d(p + 4, nch, 6, lane), frames = wave_strided_sum_d(p + 5, nch, 6, lane);
   if (lane != 0) return;
   double* __restrict__ o = out + row * WM_COLS;
   // the squares of finite f32 values cannot overflow an f64 sum: Sxx + Syy is finite exactly when every sample of the row is
@@ -154,34 +128,35 @@ __global__ __launch_bounds__(64) void wave_metrics_finalize1_kernel(const wm_par
   alpha[row] = sxy / sxx;
 }
 
-__global__ __launch_bounds__(256) void wave_metrics_pass2_kernel(const float* __restrict__ est, int64_t est_stride,
-                                                                 const float* __restrict__ ref, int64_t ref_stride, int64_t L, int cl,
-                                                                 int64_t nch, const double* __restrict__ alpha, double* __restrict__ srr) {
-  __shared__ double red[4];
+// Sum of (e - a r)^2 over one chunk (<= cl elements) of one row of length L: a = alpha[row] (SCALED, pass 2 of the wave metrics), or
+// a = 1 (the plain squared-error rows: e - r itself, without an f64 multiply by one per element).
+template <bool SCALED>
+__global__ __launch_bounds__(256) void sqerr_scaled_chunks_kernel(const float* __restrict__ est, int64_t est_stride,
+                                                                  const float* __restrict__ ref, int64_t ref_stride, int64_t L, int cl,
+                                                                  int64_t nch, const double* __restrict__ alpha, double* __restrict__ partials) {
+  __shared__ double red[4][1];
   const int64_t row = blockIdx.x / nch, c = blockIdx.x % nch;
   const int64_t start = c * cl;
   const int len = (int)(L - start < cl ? L - start : cl);
   const float* __restrict__ e = est + row * est_stride + start;
   const float* __restrict__ r = ref + row * ref_stride + start;
-  const double a = alpha[row];
+  const double a = SCALED ? alpha[row] : 1.0;
   const int tid = threadIdx.x;
   double s = 0.0;
 #pragma unroll 4
   for (int k = tid; k < len; k += 256) {
-    const double d = (double)e[k] - a * (double)r[k];
+    const double d = SCALED ? (double)e[k] - a * (double)r[k] : (double)e[k] - (double)r[k];
     s += d * d;
   }
-  s = wave_sum_d(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) srr[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = wg_reduce<WG_THREAD0, WG_SUM>(wave_sum_d(s), red, tid >> 6, tid & 63);
+  if (tid == 0) partials[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(64) void wave_metrics_finalize2_kernel(const double* __restrict__ srr_part, int64_t nch,
                                                                     const double* __restrict__ alpha, double* __restrict__ out) {
   const int64_t row = blockIdx.x;
   const int lane = threadIdx.x;
-  const double srr = qm_wave_strided_sum(srr_part + row * nch, nch, 1, lane);
+  const double srr = wave_strided_sum_d(srr_part + row * nch, nch, 1, lane);
   if (lane != 0) return;
   double* __restrict__ o = out + row * WM_COLS;
   const double a = alpha[row], sxx = o[0];          // o[0] was written by finalize 1, a launch earlier on the stream
@@ -219,34 +194,13 @@ __global__ __launch_bounds__(256) void spectrum_metrics_frames_kernel(const floa
   }
 }
 
-__global__ __launch_bounds__(256) void sqerr_chunks_kernel(const float* __restrict__ pred, const float* __restrict__ tgt, int64_t n, int64_t nch,
-                                                           double* __restrict__ partials) {
-  __shared__ double red[4];
-  const int64_t row = blockIdx.x / nch, c = blockIdx.x % nch;
-  const int64_t start = c * SQ_CH;
-  const int len = (int)(n - start < SQ_CH ? n - start : SQ_CH);
-  const float* __restrict__ p = pred + row * n + start;
-  const float* __restrict__ q = tgt + row * n + start;
-  const int tid = threadIdx.x;
-  double s = 0.0;
-#pragma unroll 4
-  for (int k = tid; k < len; k += 256) {
-    const double d = (double)p[k] - (double)q[k];
-    s += d * d;
-  }
-  s = wave_sum_d(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // one wave per row: out[row][k] = sum over the row's `per_row` partials of column k (K columns), column 1 divided by div1
 __global__ __launch_bounds__(64) void rows_sum_kernel(const double* __restrict__ partials, int64_t per_row, int K, double div1,
                                                       double* __restrict__ out) {
   const int64_t row = blockIdx.x;
   const int lane = threadIdx.x;
   for (int k = 0; k < K; ++k) {
-    const double s = qm_wave_strided_sum(partials + row * per_row * K + k, per_row, K, lane);
+    const double s = wave_strided_sum_d(partials + row * per_row * K + k, per_row, K, lane);
     if (lane == 0) out[row * K + k] = k == 1 ? s / div1 : s;
   }
 }
@@ -255,7 +209,7 @@ __global__ __launch_bounds__(64) void rows_sum_kernel(const double* __restrict__
 __global__ __launch_bounds__(64) void metric_add_sum_kernel(const double* __restrict__ vals, int64_t n, int64_t stride, double weight,
                                                             double* __restrict__ acc) {
   const int lane = threadIdx.x;
-  const double s = qm_wave_strided_sum(vals, n, stride, lane);
+  const double s = wave_strided_sum_d(vals, n, stride, lane);
   if (lane == 0) {
     acc[0] += s;
     acc[1] += (double)n * weight;
@@ -299,7 +253,7 @@ extern "C" int64_t maavss_wave_metrics_ws_bytes(int64_t B, int64_t L, int seg_le
   if (B <= 0 || L <= 0 || seg_len < 1 || seg_len > WM_CH) return 0;
   const int64_t nch = wm_chunks_per_row(L, seg_len);
   if (nch > ((int64_t)1 << 31) / B) return 0;
-  return qm_align256(B * nch * (int64_t)sizeof(wm_partial)) + qm_align256(B * nch * 8) + qm_align256(B * 8);
+  return align256(B * nch * (int64_t)sizeof(wm_partial)) + align256(B * nch * 8) + align256(B * 8);
 }
 
 extern "C" int maavss_wave_metrics(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L,
@@ -319,8 +273,8 @@ extern "C" int maavss_wave_metrics(const float* est, int64_t est_stride, const f
   MAAVSS_CHECK_ARG(ws_bytes >= need, "wave_metrics: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
   hipStream_t st = (hipStream_t)stream;
   wm_partial* partials = (wm_partial*)ws;
-  double* srr = (double*)((char*)ws + qm_align256(B * nch * (int64_t)sizeof(wm_partial)));
-  double* alpha = (double*)((char*)srr + qm_align256(B * nch * 8));
+  double* srr = (double*)((char*)ws + align256(B * nch * (int64_t)sizeof(wm_partial)));
+  double* alpha = (double*)((char*)srr + align256(B * nch * 8));
   int G = 1;
   while (G < seg_len && G < 64) G <<= 1;
   const int cl = wm_chunk_len(seg_len);
@@ -329,8 +283,8 @@ extern "C" int maavss_wave_metrics(const float* est, int64_t est_stride, const f
   MAAVSS_LAUNCH_CHECK("wave_metrics_pass1_kernel");
   hipLaunchKernelGGL(wave_metrics_finalize1_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, nch, alpha, out);
   MAAVSS_LAUNCH_CHECK("wave_metrics_finalize1_kernel");
-  hipLaunchKernelGGL(wave_metrics_pass2_kernel, dim3((unsigned)(B * nch)), dim3(256), 0, st, est, es, ref, rs, L, cl, nch, alpha, srr);
-  MAAVSS_LAUNCH_CHECK("wave_metrics_pass2_kernel");
+  hipLaunchKernelGGL(sqerr_scaled_chunks_kernel<true>, dim3((unsigned)(B * nch)), dim3(256), 0, st, est, es, ref, rs, L, cl, nch, alpha, srr);
+  MAAVSS_LAUNCH_CHECK("sqerr_scaled_chunks_kernel");
   hipLaunchKernelGGL(wave_metrics_finalize2_kernel, dim3((unsigned)B), dim3(64), 0, st, srr, nch, alpha, out);
   MAAVSS_LAUNCH_CHECK("wave_metrics_finalize2_kernel");
   return MAAVSS_OK;
@@ -338,7 +292,7 @@ extern "C" int maavss_wave_metrics(const float* est, int64_t est_stride, const f
 
 extern "C" int64_t maavss_spectrum_metrics_ws_bytes(int64_t B, int64_t T) {
   if (B <= 0 || T <= 0 || T > ((int64_t)1 << 32) / B) return 0;
-  return qm_align256(B * T * 16);
+  return align256(B * T * 16);
 }
 
 extern "C" int maavss_spectrum_metrics(const float* pred, const float* tgt, int64_t B, int64_t T, int64_t F, double lsd_floor, double* out,
@@ -368,7 +322,7 @@ extern "C" int64_t maavss_sqerr_rows_ws_bytes(int64_t B, int64_t n) {
   if (B <= 0 || n <= 0) return 0;
   const int64_t nch = (n + SQ_CH - 1) / SQ_CH;
   if (nch > ((int64_t)1 << 31) / B) return 0;
-  return qm_align256(B * nch * 8);
+  return align256(B * nch * 8);
 }
 
 extern "C" int maavss_sqerr_rows(const float* pred, const float* tgt, int64_t B, int64_t n, double* out, void* ws, int64_t ws_bytes,
@@ -384,8 +338,9 @@ extern "C" int maavss_sqerr_rows(const float* pred, const float* tgt, int64_t B,
   MAAVSS_CHECK_ARG(ws_bytes >= need, "sqerr_rows: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
   hipStream_t st = (hipStream_t)stream;
   double* partials = (double*)ws;
-  hipLaunchKernelGGL(sqerr_chunks_kernel, dim3((unsigned)(B * nch)), dim3(256), 0, st, pred, tgt, n, nch, partials);
-  MAAVSS_LAUNCH_CHECK("sqerr_chunks_kernel");
+  hipLaunchKernelGGL(sqerr_scaled_chunks_kernel<false>, dim3((unsigned)(B * nch)), dim3(256), 0, st, pred, n, tgt, n, n, SQ_CH, nch,
+                     (const double*)nullptr, partials);
+  MAAVSS_LAUNCH_CHECK("sqerr_scaled_chunks_kernel");
   hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, nch, 1, 1.0, out);
   MAAVSS_LAUNCH_CHECK("rows_sum_kernel");
   return MAAVSS_OK;

@@ -21,8 +21,6 @@ struct ts_partial {
 };
 static_assert(sizeof(ts_partial) == 32, "workspace layout of include/maavss.h");
 
-static inline int64_t ts_align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 __device__ __forceinline__ bool ts_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // Per-lane running statistics: four independent f64 chains for the sum (the FMA's latency), one chain for the rest.
@@ -50,22 +48,6 @@ struct ts_acc {
   }
 };
 
-__device__ __forceinline__ int ts_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float ts_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float ts_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // chunk table row c: chunks[3 * c + 0] = segment, + 1 = first element in buf, + 2 = length.  A row that does not lie inside [0, n)
 // or is longer than TS_CH is read as empty (the table lives on the device: the host cannot check it before the launch).
 __device__ __forceinline__ bool ts_chunk(const int64_t* __restrict__ chunks, int64_t c, int64_t n, int64_t n_segments, int64_t& seg,
@@ -80,8 +62,8 @@ __device__ __forceinline__ bool ts_chunk(const int64_t* __restrict__ chunks, int
 
 __global__ __launch_bounds__(256, 8) void tensor_stats_pass1_kernel(const float* __restrict__ buf, int64_t n, const int64_t* __restrict__ chunks,
                                                                  int64_t n_segments, ts_partial* __restrict__ partials) {
-  __shared__ double red_s[4];
-  __shared__ float red_mn[4], red_mx[4];
+  __shared__ double red_s[4][1];
+  __shared__ float red_f[4][2];
   __shared__ int red_c[4][3];
   int64_t seg, start;
   int len;
@@ -106,36 +88,17 @@ __global__ __launch_bounds__(256, 8) void tensor_stats_pass1_kernel(const float*
   } else {
     for (int i = tid; i < len; i += 256) a.add<0>(x[i]);
   }
-  double s = (a.s[0] + a.s[1]) + (a.s[2] + a.s[3]);
-  float mn = a.mn, mx = a.mx;
-  int c0 = a.n_nan, c1 = a.n_pinf, c2 = a.n_ninf;
-  s = wave_sum_d(s);
-  mn = ts_wave_min(mn);
-  mx = ts_wave_max(mx);
-  c0 = ts_wave_sum_i(c0);
-  c1 = ts_wave_sum_i(c1);
-  c2 = ts_wave_sum_i(c2);
-  const int w = tid >> 6;
-  if ((tid & 63) == 0) {
-    red_s[w] = s;
-    red_mn[w] = mn;
-    red_mx[w] = mx;
-    red_c[w][0] = c0;
-    red_c[w][1] = c1;
-    red_c[w][2] = c2;
-  }
+  const double s[1] = {wave_sum_d((a.s[0] + a.s[1]) + (a.s[2] + a.s[3]))};
+  const float f[2] = {wave_min(a.mn), wave_max(a.mx)};
+  const int k[3] = {wave_sum_i(a.n_nan), wave_sum_i(a.n_pinf), wave_sum_i(a.n_ninf)};
+  const int w = tid >> 6, lane = tid & 63;
+  wg_park(red_s, s, w, lane);      // three types behind one barrier
+  wg_park(red_f, f, w, lane);
+  wg_park(red_c, k, w, lane);
   __syncthreads();
-  if (tid == 0) {
-    ts_partial p;
-    p.sumsq = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
-    p.mn = fminf(fminf(red_mn[0], red_mn[1]), fminf(red_mn[2], red_mn[3]));
-    p.mx = fmaxf(fmaxf(red_mx[0], red_mx[1]), fmaxf(red_mx[2], red_mx[3]));
-    p.n_nan = red_c[0][0] + red_c[1][0] + red_c[2][0] + red_c[3][0];
-    p.n_pinf = red_c[0][1] + red_c[1][1] + red_c[2][1] + red_c[3][1];
-    p.n_ninf = red_c[0][2] + red_c[1][2] + red_c[2][2] + red_c[3][2];
-    p.pad = 0;
-    partials[blockIdx.x] = p;
-  }
+  if (tid == 0)
+    partials[blockIdx.x] = {wg_col<WG_SUM>(red_s, 0), wg_col<WG_MIN>(red_f, 0), wg_col<WG_MAX>(red_f, 1), wg_col<WG_SUM>(red_c, 0),
+                            wg_col<WG_SUM>(red_c, 1), wg_col<WG_SUM>(red_c, 2), 0};
 }
 
 // One workgroup of 1024 threads (16 waves).  seg_first[s] .. seg_first[s + 1] = the chunk rows of segment s (table order = buffer order).
@@ -173,11 +136,11 @@ __global__ __launch_bounds__(1024) void tensor_stats_finalize_kernel(const ts_pa
       k2 += p.n_ninf;
     }
     s = wave_sum_d(s);
-    mn = ts_wave_min(mn);
-    mx = ts_wave_max(mx);
-    k0 = ts_wave_sum_i(k0);
-    k1 = ts_wave_sum_i(k1);
-    k2 = ts_wave_sum_i(k2);
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    k0 = wave_sum_i(k0);
+    k1 = wave_sum_i(k1);
+    k2 = wave_sum_i(k2);
     if (lane == 0) {
       const bool none = mn > mx;        // no finite element: min = max = NaN
       sumsq[sg] = s;
@@ -197,9 +160,7 @@ __global__ __launch_bounds__(1024) void tensor_stats_finalize_kernel(const ts_pa
   if (!clip) return;
   __syncthreads();            // sel[] was written by this workgroup: visible to wave 0 after the barrier
   if (w != 0) return;
-  double t = 0.0;
-  for (int64_t sg = lane; sg < n_segments; sg += 64) t += sel[sg];
-  t = wave_sum_d(t);
+  const double t = wave_strided_sum_d(sel, n_segments, 1, lane);
   if (lane == 0) {
     *total_sumsq = t;
     // what IEEE arithmetic gives when the non-finite elements take part in the sum of squares: NaN with a NaN, otherwise +inf
@@ -265,7 +226,7 @@ extern "C" int maavss_tensor_stats_chunk(void) { return TS_CH; }
 
 extern "C" int64_t maavss_tensor_stats_ws_bytes(int64_t n_chunks, int64_t n_segments, int bins) {
   if (n_chunks < 0 || n_segments <= 0 || bins < 1 || bins > TS_MAX_BINS) return 0;
-  return ts_align256(n_chunks * (int64_t)sizeof(ts_partial)) + ts_align256(n_segments * 8);
+  return align256(n_chunks * (int64_t)sizeof(ts_partial)) + align256(n_segments * 8);
 }
 
 extern "C" int maavss_tensor_stats(const float* buf, int64_t n, const int64_t* chunks, int64_t n_chunks, const int* seg_first,
@@ -298,7 +259,7 @@ extern "C" int maavss_tensor_stats(const float* buf, int64_t n, const int64_t* c
                    (long long)ws_bytes, (long long)maavss_tensor_stats_ws_bytes(n_chunks, n_segments, bins));
   hipStream_t st = (hipStream_t)stream;
   ts_partial* partials = (ts_partial*)ws;
-  double* sel = (double*)((char*)ws + ts_align256(n_chunks * (int64_t)sizeof(ts_partial)));
+  double* sel = (double*)((char*)ws + align256(n_chunks * (int64_t)sizeof(ts_partial)));
   if (n_chunks > 0) {
     hipLaunchKernelGGL(tensor_stats_pass1_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, buf, n, chunks, n_segments, partials);
     MAAVSS_LAUNCH_CHECK("tensor_stats_pass1_kernel");

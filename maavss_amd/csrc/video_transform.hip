@@ -33,18 +33,16 @@ __host__ __device__ inline int vt_taps(int in, int S, int antialias) {
   return antialias ? 2 * (int)((in + S - 1) / S) + 3 : 2;
 }
 
-inline int64_t vt_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 inline VtLayout vt_layout(int64_t F, int clip_frames, int H0, int W0, int S, int antialias, int autocontrast) {
   VtLayout L;
   const int64_t nclips = F / clip_frames;
   L.ty = vt_taps(H0, S, antialias);
   L.tx = vt_taps(W0, S, antialias);
   L.ranges = 0;                                                           // int32 [clip][2 axes][S][2] (start, count)
-  L.wy = vt_align(nclips * 2 * S * 2 * 4);                                // f32 [clip][ty][S]
-  L.wx = L.wy + vt_align(nclips * (int64_t)L.ty * S * 4);                 // f32 [clip][tx][S]
-  L.keys = L.wx + vt_align(nclips * (int64_t)L.tx * S * 4);               // int32 [F][3][2] (min key, max key)
-  L.total = L.keys + (autocontrast ? vt_align(F * 6 * 4) : 0);
+  L.wy = align256(nclips * 2 * S * 2 * 4);                                // f32 [clip][ty][S]
+  L.wx = L.wy + align256(nclips * (int64_t)L.ty * S * 4);                 // f32 [clip][tx][S]
+  L.keys = L.wx + align256(nclips * (int64_t)L.tx * S * 4);               // int32 [F][3][2] (min key, max key)
+  L.total = L.keys + (autocontrast ? align256(F * 6 * 4) : 0);
   return L;
 }
 
@@ -169,22 +167,12 @@ __global__ __launch_bounds__(256) void video_transform_kernel(const uint8_t* __r
   if (keys == nullptr) return;                         // uniform over the grid
   __shared__ float red[VT_BY][6];
   const int wave = threadIdx.y;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float l = -wave_max(-lo[c]), u = wave_max(hi[c]);
-    if (threadIdx.x == 0) {
-      red[wave][2 * c] = l;
-      red[wave][2 * c + 1] = u;
-    }
-  }
+  const float v[6] = {wave_min(lo[0]), wave_max(hi[0]), wave_min(lo[1]), wave_max(hi[1]), wave_min(lo[2]), wave_max(hi[2])};
+  wg_park(red, v, wave, threadIdx.x);
   __syncthreads();
-  if (wave == 0 && threadIdx.x < 3) {
+  if (wave == 0 && threadIdx.x < 3) {                  // a lane per channel
     const int c = threadIdx.x;
-    float l = red[0][2 * c], u = red[0][2 * c + 1];
-    for (int q = 1; q < VT_BY; ++q) {
-      l = fminf(l, red[q][2 * c]);
-      u = fmaxf(u, red[q][2 * c + 1]);
-    }
+    const float l = wg_col<WG_MIN>(red, 2 * c), u = wg_col<WG_MAX>(red, 2 * c + 1);
     if (l <= u) {                                      // the block holds at least one pixel of this frame
       atomicMin(keys + (f * 3 + c) * 2, vt_key(l));
       atomicMax(keys + (f * 3 + c) * 2 + 1, vt_key(u));

@@ -18,7 +18,7 @@ Nothing here synchronises with the host before `Validator.result()`.
 """
 import torch
 
-from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr
+from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr, workspace
 from .trainer import sliding_windows
 
 WAVE_COLUMNS = ("sxx", "syy", "sxy", "see", "srr", "snr_db", "si_sdr_db", "seg_snr_db", "n_frames")
@@ -55,10 +55,6 @@ def _rows(t, what):
     return t
 
 
-def _ws(nbytes, dev):
-    return torch.empty(max(int(nbytes), 8) // 8, dtype=torch.float64, device=dev)
-
-
 def wave_metrics(est, ref, seg_len=256):
     """est, ref: f32 cuda [L] or [B, L], samples contiguous, any row stride >= 0 (rows may overlap) and any 4-byte-aligned offset -- a slice
     `clean[start:start + n]` is taken as it is.  -> dict of device f64 tensors [B]: sxx, syy, sxy, see, srr, snr_db, si_sdr_db, seg_snr_db,
@@ -73,7 +69,7 @@ def wave_metrics(est, ref, seg_len=256):
     b, n = est.shape
     out = torch.empty(b, len(WAVE_COLUMNS), dtype=torch.float64, device=est.device)
     nbytes = int(query("maavss_wave_metrics_ws_bytes", b, n, int(seg_len)))
-    ws = _ws(nbytes, est.device)
+    ws = workspace(nbytes, est.device)
     call("maavss_wave_metrics", ptr(est), est.stride(0), ptr(ref), ref.stride(0), b, n, int(seg_len), ptr(out), ptr(ws), nbytes, stream_ptr())
     res = {k: out[:, i] for i, k in enumerate(WAVE_COLUMNS)}
     res["raw"] = out
@@ -96,7 +92,7 @@ def spectrum_metrics(pred, tgt, lsd_floor=1e-10):
     b, _, t, f = pred.shape
     out = torch.empty(b, 2, dtype=torch.float64, device=pred.device)
     nbytes = int(query("maavss_spectrum_metrics_ws_bytes", b, t))
-    ws = _ws(nbytes, pred.device)
+    ws = workspace(nbytes, pred.device)
     call("maavss_spectrum_metrics", ptr(pred), ptr(tgt), b, t, f, float(lsd_floor), ptr(out), ptr(ws), nbytes, stream_ptr())
     return {"sqerr": out[:, 0], "lsd_db": out[:, 1], "raw": out}
 
@@ -111,7 +107,7 @@ def sqerr_rows(pred, tgt):
     n = pred.numel() // b
     out = torch.empty(b, dtype=torch.float64, device=pred.device)
     nbytes = int(query("maavss_sqerr_rows_ws_bytes", b, n))
-    ws = _ws(nbytes, pred.device)
+    ws = workspace(nbytes, pred.device)
     call("maavss_sqerr_rows", ptr(pred), ptr(tgt), b, n, ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 

@@ -13,7 +13,7 @@ device for `maavss_adam_step_dscale`.
 """
 import numpy as np
 
-from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr
+from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr, workspace
 
 MAX_BINS = 1024
 
@@ -80,7 +80,7 @@ class TensorStats:
         self._mask = torch.ones(s, dtype=torch.int32, device=dev)
         self._mask_key = None                      # names the mask on the device stands for (None = all)
         self._ws_bytes = int(query("maavss_tensor_stats_ws_bytes", self.n_chunks, s, self.bins))
-        self._ws = torch.empty(max(self._ws_bytes, 8) // 8 + 1, dtype=torch.float64, device=dev)
+        self._ws = workspace(self._ws_bytes, dev)      # the entry point asks for ws_bytes and no more: no spare element
         # one output buffer: [sumsq f64 x S | total_sumsq f64 | min f32 x S | max f32 x S | norm f32 | scale f32 | nonfinite i32 x 3S | hist i32 x S*bins]
         self._lay, o = {}, 0
         for key, dt, cnt in (("sumsq", np.float64, s), ("total_sumsq", np.float64, 1), ("min", np.float32, s), ("max", np.float32, s),

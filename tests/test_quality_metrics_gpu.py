@@ -163,7 +163,8 @@ def test_spectrum_metrics_keep_a_nan():
 def test_squared_error_rows_equal_the_twin(b):
     sq = int(maavss_amd._lib.query("maavss_sqerr_rows_chunk"))
     rng = np.random.default_rng(b)
-    for n in (1, 255, 257, sq - 1, sq, sq + 1, 2 * sq + 5):
+    # 63 .. 65 and 255 .. 257: an empty wave, a partly filled fourth wave; around sq: the last short chunk (the kernel is pass 2's, without alpha)
+    for n in (1, 63, 64, 65, 255, 256, 257, sq - 1, sq, sq + 1, 2 * sq + 3, 2 * sq + 5):
         pred = rng.standard_normal((b, n)).astype(np.float32)
         tgt = (pred + 0.1 * rng.standard_normal((b, n))).astype(np.float32)
         got = _host(quality.sqerr_rows(torch.from_numpy(pred).cuda(), torch.from_numpy(tgt).cuda()))
