@@ -9,10 +9,7 @@
 //   bn_bwd_finalize   partials -> dgamma, dbeta, and the three per-channel constants of the dx formula
 //   bn_pool_act_bwd_dx       dy = gamma*invstd * (g_at_argmax - mean(g) - xhat * mean(g*xhat))   (dense, full res)
 #include "common.h"
-
-#define ACT_LEAKY 0
-#define BN_INV_MIN_GAMMA 1e-2f
-#define ACT_TANH 1
+#include "bn_act.h"      // the per-element arithmetic: affine, pool tie rule, activations, the dy formula, the two finalize bodies
 
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y, float* __restrict__ partials,
                                                        int64_t M, int C, int rows_per_block) {
@@ -87,18 +84,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
   double s1, s2;
   bn_sum_partials(partials, nblk, C, s1, s2);
   const int c = threadIdx.x;
-  if (c < C) {
-    const double m = s1 / count;
-    double var = s2 / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean != nullptr) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
-      running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
-    }
-  }
+  if (c < C) bn_finalize_channel(c, s1, s2, count, eps, momentum, mean, invstd, running_mean, running_var);
   if (c == 0 && num_batches_tracked != nullptr) *num_batches_tracked += 1;
 }
 
@@ -115,11 +101,6 @@ struct PoolGeom {
 // come from scalar divisions once per row), a thread's channel block is the same for every element it ever touches (256 is a multiple of C / 4:
 // the per-channel constants are loaded once), x is a shift, the pool size is a template constant, and offsets inside a row are 32-bit.
 
-__device__ __forceinline__ float act_fwd(float v, int act) { return act == ACT_TANH ? tanhf(v) : (v > 0.f ? v : 0.01f * v); }
-__device__ __forceinline__ float act_bwd_from_out(float out, int act) {
-  return act == ACT_TANH ? 1.f - out * out : (out > 0.f ? 1.f : 0.01f);
-}
-
 // every thread handles 4 consecutive channels of one (pooled) position: float4 traffic on the channels-last side; a workgroup walks pooled rows
 template <int P>
 __global__ __launch_bounds__(256) void bn_pool_act_fwd_kernel(const float* __restrict__ y, const float* __restrict__ mean,
@@ -132,8 +113,9 @@ __global__ __launch_bounds__(256) void bn_pool_act_fwd_kernel(const float* __res
   const int c = (tid & (C4 - 1)) * 4;                 // the same for every element of this thread (256 % C4 == 0)
   const float4 ga = *reinterpret_cast<const float4*>(gamma + c), is = *reinterpret_cast<const float4*>(invstd + c);
   const float4 be = *reinterpret_cast<const float4*>(beta + c), mu = *reinterpret_cast<const float4*>(mean + c);
-  const float sc[4] = {ga.x * is.x, ga.y * is.y, ga.z * is.z, ga.w * is.w};
-  const float sh[4] = {be.x - mu.x * sc[0], be.y - mu.y * sc[1], be.z - mu.z * sc[2], be.w - mu.w * sc[3]};
+  float sc[4], sh[4];
+  bn_scale_shift(ga.x, is.x, be.x, mu.x, sc[0], sh[0]); bn_scale_shift(ga.y, is.y, be.y, mu.y, sc[1], sh[1]);
+  bn_scale_shift(ga.z, is.z, be.z, mu.z, sc[2], sh[2]); bn_scale_shift(ga.w, is.w, be.w, mu.w, sc[3], sh[3]);
   const int rows = g.BT * g.Hp, n = g.Wp * C4;
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {      // block-uniform: scalar arithmetic
     const int bt = row / g.Hp, py = row - bt * g.Hp, b = bt / g.T, t = bt - b * g.T;
@@ -152,10 +134,10 @@ __global__ __launch_bounds__(256) void bn_pool_act_fwd_kernel(const float* __res
         for (int dx = 0; dx < P; ++dx) v4[dy * P + dx] = *reinterpret_cast<const float4*>(yp + (dy * g.W + dx) * C);
 #pragma unroll
       for (int q = 0; q < P * P; ++q) {
-        const float v[4] = {v4[q].x * sc[0] + sh[0], v4[q].y * sc[1] + sh[1], v4[q].z * sc[2] + sh[2], v4[q].w * sc[3] + sh[3]};
+        const float v[4] = {bn_affine(v4[q].x, sc[0], sh[0]), bn_affine(v4[q].y, sc[1], sh[1]), bn_affine(v4[q].z, sc[2], sh[2]), bn_affine(v4[q].w, sc[3], sh[3])};
 #pragma unroll
         for (int e2 = 0; e2 < 4; ++e2)
-          if (v[e2] > best[e2] || (v[e2] != v[e2] && best[e2] == best[e2])) { best[e2] = v[e2]; bi[e2] = q; }      // q = dy * P + dx
+          if (pool_take(v[e2], best[e2])) { best[e2] = v[e2]; bi[e2] = q; }      // q = dy * P + dx
       }
       float* op = orow + px * g.osP;
       const float a4[4] = {act_fwd(best[0], act), act_fwd(best[1], act), act_fwd(best[2], act), act_fwd(best[3], act)};
@@ -242,7 +224,7 @@ __global__ __launch_bounds__(256) void bn_pool_act_bwd_reduce_kernel(
         const float gg = dv[u][e] * act_bwd_from_out(ov[u][e], act);
         float xh;
         if (inv[e]) {
-          xh = ov[u][e] > 0.f ? ov[u][e] : ov[u][e] * 100.f;          // z = LeakyReLU(0.01)^-1 (out)
+          xh = leaky_inv(ov[u][e]);                                   // z = LeakyReLU(0.01)^-1 (out)
         } else {
           const int iy = pys[u] * g.p + bi[e] / g.p, ix = pxs[u] * g.p + bi[e] % g.p;
           xh = (y[(((int64_t)bts[u] * g.H + iy) * g.W + ix) * C + c + e] - mu[e]) * is[e];
@@ -276,14 +258,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
   bn_sum_partials(partials, nblk, C, s1, s2);
   const int c = threadIdx.x;
   if (c >= C) return;
-  if (beta_inv != nullptr && fabsf(gamma[c]) >= BN_INV_MIN_GAMMA) s2 = (s2 - (double)beta_inv[c] * s1) / (double)gamma[c];
-  if (dgamma != nullptr) {
-    dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s2;
-    dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s1;
-  }
-  coef[c] = gamma[c] * invstd[c];
-  coef[C + c] = (float)(s1 / count);
-  coef[2 * C + c] = (float)(s2 / count);
+  bn_bwd_finalize_channel(c, C, s1, s2, s1, s2, count, gamma, invstd, dgamma, dbeta, accumulate, coef, beta_inv);      // local sums = global sums
 }
 
 template <bool DY16, int P>
@@ -324,10 +299,10 @@ __global__ __launch_bounds__(256) void bn_pool_act_bwd_dx_kernel(
         }
       }
       float4 o;
-      o.x = k0.x * (gg[0] - k1.x - (yv.x - mu.x) * is.x * k2.x);
-      o.y = k0.y * (gg[1] - k1.y - (yv.y - mu.y) * is.y * k2.y);
-      o.z = k0.z * (gg[2] - k1.z - (yv.z - mu.z) * is.z * k2.z);
-      o.w = k0.w * (gg[3] - k1.w - (yv.w - mu.w) * is.w * k2.w);
+      o.x = bn_dy(gg[0], yv.x, mu.x, is.x, k0.x, k1.x, k2.x);
+      o.y = bn_dy(gg[1], yv.y, mu.y, is.y, k0.y, k1.y, k2.y);
+      o.z = bn_dy(gg[2], yv.z, mu.z, is.z, k0.z, k1.z, k2.z);
+      o.w = bn_dy(gg[3], yv.w, mu.w, is.w, k0.w, k1.w, k2.w);
       // DY16: both consumers of dy (the input-gradient and the weight-gradient MFMA kernels) round it to bf16 when they stage
       // it -- rounded here once instead (bit-identical operands), written and re-read at half the bytes
       const int64_t di = rbase + (int64_t)ix * C;
@@ -337,9 +312,10 @@ __global__ __launch_bounds__(256) void bn_pool_act_bwd_dx_kernel(
   }
 }
 
+static bool c_ok(int C) { return C >= 4 && C <= 64 && (C & (C - 1)) == 0; }      // four channels per thread, 256 or 1024 threads divided by C
 static int check_geom(const char* who, int B, int T, int H, int W, int C, int p) {
   MAAVSS_CHECK_ARG(B > 0 && T > 0 && H > 0 && W > 0, "%s: empty tensor", who);
-  MAAVSS_CHECK_ARG(C >= 4 && C <= 64 && (C & (C - 1)) == 0, "%s: C must be a power of two in [4, 64] (got %d)", who, C);
+  MAAVSS_CHECK_ARG(c_ok(C), "%s: C must be a power of two in [4, 64] (got %d)", who, C);
   MAAVSS_CHECK_ARG(p >= 1 && p <= 3, "%s: pool must be 1, 2 or 3", who);
   MAAVSS_CHECK_ARG(H / p > 0 && W / p > 0, "%s: pooled size is zero", who);
   MAAVSS_CHECK_ARG((int64_t)B * T * H < (1LL << 31) && (int64_t)B * T * (H / p) * (W / p) < (1LL << 31), "%s: too many rows for the 32-bit row arithmetic", who);
@@ -365,7 +341,7 @@ extern "C" int maavss_bn_stats_nblk(int64_t rows) {
 
 extern "C" int maavss_bn_stats(const float* y, float* partials, int64_t rows, int C, void* stream) {
   MAAVSS_CHECK_ARG(y && partials && rows > 0, "bn_stats: bad arguments");
-  MAAVSS_CHECK_ARG(C >= 4 && C <= 64 && (C & (C - 1)) == 0, "bn_stats: C must be a power of two in [4, 64]");
+  MAAVSS_CHECK_ARG(c_ok(C), "bn_stats: C must be a power of two in [4, 64]");
   const int nblk = maavss_bn_stats_nblk(rows);
   const int rpb = cdiv(rows, nblk);
   hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, y, partials, rows, C, rpb);
@@ -373,17 +349,22 @@ extern "C" int maavss_bn_stats(const float* y, float* partials, int64_t rows, in
   return MAAVSS_OK;
 }
 
+// two-level reduction of more than 512 partial rows: 256 blocks fold them first (ws: 256*2*C floats) and stand in for them
+static int fold_partials(const float*& partials, int& nblk, int C, float* ws, hipStream_t st) {
+  if (nblk <= 512 || ws == nullptr) return MAAVSS_OK;
+  const int rpb = cdiv(nblk, 256), nb1 = cdiv(nblk, rpb);
+  hipLaunchKernelGGL(bn_reduce_rows_kernel, dim3(nb1), dim3(256), 0, st, partials, ws, nblk, 2 * C, rpb);
+  MAAVSS_LAUNCH_CHECK("bn_reduce_rows_kernel");
+  partials = ws;
+  nblk = nb1;
+  return MAAVSS_OK;
+}
+
 extern "C" int maavss_bn_finalize(const float* partials, int nblk, int C, double count, float eps, float momentum,
                                   float* mean, float* invstd, float* running_mean, float* running_var,
                                   void* num_batches_tracked, float* ws, void* stream) {
-  MAAVSS_CHECK_ARG(partials && mean && invstd && nblk > 0 && C > 0 && C <= 64, "bn_finalize: bad arguments");
-  if (nblk > 512 && ws != nullptr) {  // two-level reduction: 256 blocks fold the partial rows first (ws: 256*2*C floats)
-    const int rpb = cdiv(nblk, 256), nb1 = cdiv(nblk, rpb);
-    hipLaunchKernelGGL(bn_reduce_rows_kernel, dim3(nb1), dim3(256), 0, (hipStream_t)stream, partials, ws, nblk, 2 * C, rpb);
-    MAAVSS_LAUNCH_CHECK("bn_reduce_rows_kernel");
-    partials = ws;
-    nblk = nb1;
-  }
+  MAAVSS_CHECK_ARG(partials && mean && invstd && nblk > 0 && c_ok(C), "bn_finalize: bad arguments");
+  if (int rc = fold_partials(partials, nblk, C, ws, (hipStream_t)stream)) return rc;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partials, nblk, C, count, eps, momentum,
                      mean, invstd, running_mean, running_var, (long long*)num_batches_tracked);
   MAAVSS_LAUNCH_CHECK("bn_finalize_kernel");
@@ -402,7 +383,7 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ running_mean, con
 
 extern "C" int maavss_bn_eval_stats(const float* running_mean, const float* running_var, float eps, float* mean, float* invstd,
                                     int C, void* stream) {
-  MAAVSS_CHECK_ARG(running_mean && running_var && mean && invstd && C > 0 && C <= 64, "bn_eval_stats: bad arguments");
+  MAAVSS_CHECK_ARG(running_mean && running_var && mean && invstd && c_ok(C), "bn_eval_stats: bad arguments");
   hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, running_mean, running_var, eps, mean,
                      invstd, C);
   MAAVSS_LAUNCH_CHECK("bn_eval_stats_kernel");
@@ -418,30 +399,37 @@ extern "C" int maavss_bn_pool_act_fwd(const float* y, const float* mean, const f
   MAAVSS_CHECK_ARG(pool == 1 || argmax != nullptr, "bn_pool_act_fwd: argmax buffer required when pool > 1");
   PoolGeom g = make_geom(B, T, H, W, C, pool, os_b, os_t, os_p, os_c);
   const dim3 grid(min(g.BT * g.Hp, 4096));      // a workgroup walks pooled rows
-#define FWD_LAUNCH(P) hipLaunchKernelGGL(bn_pool_act_fwd_kernel<P>, grid, dim3(256), 0, (hipStream_t)stream, y, mean, invstd, gamma, beta, out, \
-                                         (unsigned char*)argmax, (unsigned short*)out16, (unsigned short*)out_bf16, g, act)
-  if (pool == 1) FWD_LAUNCH(1);
-  else if (pool == 2) FWD_LAUNCH(2);
-  else FWD_LAUNCH(3);
-#undef FWD_LAUNCH
+  auto kern = pool == 1 ? bn_pool_act_fwd_kernel<1> : pool == 2 ? bn_pool_act_fwd_kernel<2> : bn_pool_act_fwd_kernel<3>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, y, mean, invstd, gamma, beta, out, (unsigned char*)argmax, (unsigned short*)out16,
+                     (unsigned short*)out_bf16, g, act);
   MAAVSS_LAUNCH_CHECK("bn_pool_act_fwd_kernel");
   return MAAVSS_OK;
 }
 
-// ws: at least (2*C*nblk + 3*C) floats with nblk = maavss_bn_stats_nblk(B*T*Hp*Wp); coef = ws + 2*C*nblk
-#define BN_DX_LAUNCH()                                                                                                        \
-  {                                                                                                                           \
-    const dim3 grid(min(g.BT * H, 4096));      /* a workgroup walks rows */                                                   \
-    const unsigned char* am_ = (const unsigned char*)argmax;                                                                  \
-    if (dy_bf16 && g.p == 1) hipLaunchKernelGGL((bn_pool_act_bwd_dx_kernel<true, 1>), grid, dim3(256), 0, st, dout, out, am_, y, mean, invstd, coef, dy, g, act);      \
-    else if (dy_bf16 && g.p == 2) hipLaunchKernelGGL((bn_pool_act_bwd_dx_kernel<true, 2>), grid, dim3(256), 0, st, dout, out, am_, y, mean, invstd, coef, dy, g, act); \
-    else if (dy_bf16) hipLaunchKernelGGL((bn_pool_act_bwd_dx_kernel<true, 3>), grid, dim3(256), 0, st, dout, out, am_, y, mean, invstd, coef, dy, g, act);             \
-    else if (g.p == 1) hipLaunchKernelGGL((bn_pool_act_bwd_dx_kernel<false, 1>), grid, dim3(256), 0, st, dout, out, am_, y, mean, invstd, coef, dy, g, act);           \
-    else if (g.p == 2) hipLaunchKernelGGL((bn_pool_act_bwd_dx_kernel<false, 2>), grid, dim3(256), 0, st, dout, out, am_, y, mean, invstd, coef, dy, g, act);           \
-    else hipLaunchKernelGGL((bn_pool_act_bwd_dx_kernel<false, 3>), grid, dim3(256), 0, st, dout, out, am_, y, mean, invstd, coef, dy, g, act);                          \
-    MAAVSS_LAUNCH_CHECK("bn_pool_act_bwd_dx_kernel");                                                                         \
-  }
+// The pieces the unsplit and the split backward share.
+static bool bwd_inverse(const float* beta, int act) { return beta != nullptr && act == ACT_LEAKY; }   // tanh^-1 is ill-conditioned near +-1: those layers gather
 
+// the reduction pass: *nblk = maavss_bn_stats_nblk(pooled rows) partial rows [2][C] into ws
+static int bwd_reduce_launch(const float* dout, const float* out, const void* argmax, const float* y, const float* mean, const float* invstd,
+                             const float* gamma, const float* beta, float* ws, const PoolGeom& g, int act, int* nblk, hipStream_t st) {
+  const int64_t rows = (int64_t)g.BT * g.Hp * g.Wp;
+  *nblk = maavss_bn_stats_nblk(rows);
+  hipLaunchKernelGGL(bn_pool_act_bwd_reduce_kernel, dim3(*nblk), dim3(256), 0, st, dout, out, (const unsigned char*)argmax,
+                     y, mean, invstd, bwd_inverse(beta, act) ? gamma : nullptr, ws, g, act, (int64_t)cdiv(rows, *nblk));
+  MAAVSS_LAUNCH_CHECK("bn_pool_act_bwd_reduce_kernel");
+  return MAAVSS_OK;
+}
+
+static int bwd_dx_launch(const float* dout, const float* out, const void* argmax, const float* y, const float* mean, const float* invstd,
+                         const float* coef, void* dy, int dy_bf16, const PoolGeom& g, int act, hipStream_t st) {
+  auto kern = dy_bf16 ? (g.p == 1 ? bn_pool_act_bwd_dx_kernel<true, 1> : g.p == 2 ? bn_pool_act_bwd_dx_kernel<true, 2> : bn_pool_act_bwd_dx_kernel<true, 3>)
+                      : (g.p == 1 ? bn_pool_act_bwd_dx_kernel<false, 1> : g.p == 2 ? bn_pool_act_bwd_dx_kernel<false, 2> : bn_pool_act_bwd_dx_kernel<false, 3>);
+  hipLaunchKernelGGL(kern, dim3(min(g.BT * g.H, 4096)), dim3(256), 0, st, dout, out, (const unsigned char*)argmax, y, mean, invstd, coef, dy, g, act);
+  MAAVSS_LAUNCH_CHECK("bn_pool_act_bwd_dx_kernel");
+  return MAAVSS_OK;
+}
+
+// ws: at least (2*C*nblk + 3*C) floats with nblk = maavss_bn_stats_nblk(B*T*Hp*Wp); coef = ws + 2*C*nblk
 extern "C" int maavss_bn_pool_act_bwd(const float* dout, const float* out, const void* argmax, const float* y,
                                       const float* mean, const float* invstd, const float* gamma, const float* beta, void* dy,
                                       float* dgamma, float* dbeta, int accumulate, float* ws, int B, int T, int H, int W,
@@ -452,20 +440,15 @@ extern "C" int maavss_bn_pool_act_bwd(const float* dout, const float* out, const
   MAAVSS_CHECK_ARG(pool == 1 || argmax != nullptr, "bn_pool_act_bwd: argmax buffer required when pool > 1");
   hipStream_t st = (hipStream_t)stream;
   PoolGeom g = make_geom(B, T, H, W, C, pool, os_b, os_t, os_p, os_c);
-  const int64_t rows = (int64_t)g.BT * g.Hp * g.Wp;
-  const int nblk = maavss_bn_stats_nblk(rows);
+  int nblk;
+  if (int rc = bwd_reduce_launch(dout, out, argmax, y, mean, invstd, gamma, beta, ws, g, act, &nblk, st)) return rc;
   float* coef = ws + (int64_t)2 * C * nblk;
-  const bool inverse = beta != nullptr && act == ACT_LEAKY;   // tanh^-1 is ill-conditioned near +-1: those layers gather
-  hipLaunchKernelGGL(bn_pool_act_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, st, dout, out, (const unsigned char*)argmax,
-                     y, mean, invstd, inverse ? gamma : nullptr, ws, g, act, (int64_t)cdiv(rows, nblk));
-  MAAVSS_LAUNCH_CHECK("bn_pool_act_bwd_reduce_kernel");
   const double count = (double)g.BT * H * W;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(1), dim3(1024), 0, st, ws, nblk, C, count, gamma, invstd, dgamma, dbeta,
-                     accumulate, coef, inverse ? beta : nullptr);
+                     accumulate, coef, bwd_inverse(beta, act) ? beta : nullptr);
   MAAVSS_LAUNCH_CHECK("bn_bwd_finalize_kernel");
   if (dy == nullptr) return MAAVSS_OK;   // the consumer applies the coefficients itself (maavss_conv3d_c1_wgrad_bn)
-  BN_DX_LAUNCH()
-  return MAAVSS_OK;
+  return bwd_dx_launch(dout, out, argmax, y, mean, invstd, coef, dy, dy_bf16, g, act, st);
 }
 
 // ---- split forms for cross-rank (global-batch) BatchNorm statistics: the per-channel sums leave the device-side
@@ -488,19 +471,7 @@ __global__ void bn_finalize_sums_kernel(const double* __restrict__ sums, int C, 
                                         float* __restrict__ invstd, float* __restrict__ running_mean,
                                         float* __restrict__ running_var, long long* __restrict__ num_batches_tracked) {
   const int c = threadIdx.x;
-  const double count = sums[2 * C];
-  if (c < C) {
-    const double m = sums[c] / count;
-    double var = sums[C + c] / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean != nullptr) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
-      running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
-    }
-  }
+  if (c < C) bn_finalize_channel(c, sums[c], sums[C + c], sums[2 * C], eps, momentum, mean, invstd, running_mean, running_var);
   if (c == 0 && num_batches_tracked != nullptr) *num_batches_tracked += 1;
 }
 
@@ -511,32 +482,13 @@ __global__ void bn_bwd_finalize_sums_kernel(const double* __restrict__ local, co
                                             float* __restrict__ coef, const float* __restrict__ beta_inv) {
   const int c = threadIdx.x;
   if (c >= C) return;
-  const bool inv = beta_inv != nullptr && fabsf(gamma[c]) >= BN_INV_MIN_GAMMA;
-  double l1 = local[c], l2 = local[C + c], g1 = global[c], g2 = global[C + c];
-  if (inv) {
-    l2 = (l2 - (double)beta_inv[c] * l1) / (double)gamma[c];
-    g2 = (g2 - (double)beta_inv[c] * g1) / (double)gamma[c];
-  }
-  if (dgamma != nullptr) {
-    dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)l2;
-    dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)l1;
-  }
-  const double count = global[2 * C];
-  coef[c] = gamma[c] * invstd[c];
-  coef[C + c] = (float)(g1 / count);
-  coef[2 * C + c] = (float)(g2 / count);
+  bn_bwd_finalize_channel(c, C, local[c], local[C + c], global[c], global[C + c], global[2 * C], gamma, invstd, dgamma, dbeta, accumulate, coef, beta_inv);
 }
 
 extern "C" int maavss_bn_partials_to_sums(const float* partials, int nblk, int C, double count, double* sums, float* ws,
                                           void* stream) {
-  MAAVSS_CHECK_ARG(partials && sums && nblk > 0 && C > 0 && C <= 64 && count > 0, "bn_partials_to_sums: bad arguments");
-  if (nblk > 512 && ws != nullptr) {
-    const int rpb = cdiv(nblk, 256), nb1 = cdiv(nblk, rpb);
-    hipLaunchKernelGGL(bn_reduce_rows_kernel, dim3(nb1), dim3(256), 0, (hipStream_t)stream, partials, ws, nblk, 2 * C, rpb);
-    MAAVSS_LAUNCH_CHECK("bn_reduce_rows_kernel");
-    partials = ws;
-    nblk = nb1;
-  }
+  MAAVSS_CHECK_ARG(partials && sums && nblk > 0 && c_ok(C) && count > 0, "bn_partials_to_sums: bad arguments");
+  if (int rc = fold_partials(partials, nblk, C, ws, (hipStream_t)stream)) return rc;
   hipLaunchKernelGGL(bn_sums_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partials, nblk, C, count, sums);
   MAAVSS_LAUNCH_CHECK("bn_sums_kernel");
   return MAAVSS_OK;
@@ -544,7 +496,7 @@ extern "C" int maavss_bn_partials_to_sums(const float* partials, int nblk, int C
 
 extern "C" int maavss_bn_finalize_sums(const double* sums, int C, float eps, float momentum, float* mean, float* invstd,
                                        float* running_mean, float* running_var, void* num_batches_tracked, void* stream) {
-  MAAVSS_CHECK_ARG(sums && mean && invstd && C > 0 && C <= 64, "bn_finalize_sums: bad arguments");
+  MAAVSS_CHECK_ARG(sums && mean && invstd && c_ok(C), "bn_finalize_sums: bad arguments");
   hipLaunchKernelGGL(bn_finalize_sums_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, C, eps, momentum, mean, invstd,
                      running_mean, running_var, (long long*)num_batches_tracked);
   MAAVSS_LAUNCH_CHECK("bn_finalize_sums_kernel");
@@ -560,12 +512,8 @@ extern "C" int maavss_bn_pool_act_bwd_sums(const float* dout, const float* out, 
   MAAVSS_CHECK_ARG(pool == 1 || argmax != nullptr, "bn_pool_act_bwd_sums: argmax buffer required when pool > 1");
   hipStream_t st = (hipStream_t)stream;
   PoolGeom g = make_geom(B, T, H, W, C, pool, os_b, os_t, os_p, os_c);
-  const int64_t rows = (int64_t)g.BT * g.Hp * g.Wp;
-  const int nblk = maavss_bn_stats_nblk(rows);
-  const bool inverse = beta != nullptr && act == ACT_LEAKY;
-  hipLaunchKernelGGL(bn_pool_act_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, st, dout, out, (const unsigned char*)argmax,
-                     y, mean, invstd, inverse ? gamma : nullptr, ws, g, act, (int64_t)cdiv(rows, nblk));
-  MAAVSS_LAUNCH_CHECK("bn_pool_act_bwd_reduce_kernel");
+  int nblk;
+  if (int rc = bwd_reduce_launch(dout, out, argmax, y, mean, invstd, gamma, beta, ws, g, act, &nblk, st)) return rc;
   hipLaunchKernelGGL(bn_sums_kernel, dim3(1), dim3(1024), 0, st, ws, nblk, C, (double)g.BT * H * W, sums);
   MAAVSS_LAUNCH_CHECK("bn_sums_kernel");
   return MAAVSS_OK;
@@ -581,11 +529,9 @@ extern "C" int maavss_bn_pool_act_bwd_finish(const float* dout, const float* out
   if (int rc = check_geom("bn_pool_act_bwd_finish", B, T, H, W, C, pool)) return rc;
   hipStream_t st = (hipStream_t)stream;
   PoolGeom g = make_geom(B, T, H, W, C, pool, os_b, os_t, os_p, os_c);
-  const bool inverse = beta != nullptr && act == ACT_LEAKY;
   hipLaunchKernelGGL(bn_bwd_finalize_sums_kernel, dim3(1), dim3(64), 0, st, sums_local, sums_global, C, gamma, invstd, dgamma,
-                     dbeta, accumulate, coef, inverse ? beta : nullptr);
+                     dbeta, accumulate, coef, bwd_inverse(beta, act) ? beta : nullptr);
   MAAVSS_LAUNCH_CHECK("bn_bwd_finalize_sums_kernel");
   if (dy == nullptr) return MAAVSS_OK;
-  BN_DX_LAUNCH()
-  return MAAVSS_OK;
+  return bwd_dx_launch(dout, out, argmax, y, mean, invstd, coef, dy, dy_bf16, g, act, st);
 }

@@ -7,6 +7,7 @@
 // conv3d_c1_wgrad_kernel<false|true>, an exact-f32 direct convolution on the VALU from an LDS halo tile, weights as wave-uniform scalar operands.
 // The per-chunk partials of all three weight-gradient kernels are summed by conv3d_c1_wgrad_reduce_kernel (conv3d_wgrad.hip).
 #include "conv3d_tile.h"
+#include "bn_act.h"      // the BatchNorm / pool / LeakyReLU scalars this file shares with bn_pool.hip
 
 // value of element i of the [3][20][20] f32 halo of the tile at (bt, t, y0, x0): zero outside the clip and the frame
 __device__ __forceinline__ float c1_halo_f32(const float* __restrict__ x, int i, int bt, int t, int y0, int x0, int T, int H, int W) {
@@ -91,11 +92,10 @@ __global__ __launch_bounds__(256) void conv3d_c1_fwd_kernel(const float* __restr
 //                                   BN_INV_MIN_GAMMA: the backward reduction then has to gather xhat from y, bn_pool.hip);
 //   EPI 2  (conv3d_c1_bn_pool_act)  conv again -> gamma (y - mean) invstd + beta -> 2x2 max pool -> LeakyReLU: the pooled
 //                                   activation (f32 + IEEE half) and the argmax byte, bit-identical to bn_pool_act_fwd_kernel on
-//                                   the stored y (same expressions, same scan order dy, dx, first maximum wins, NaN sticks);
+//                                   the stored y (the scalars of bn_act.h in the same scan order dy, dx);
 //   conv3d_c1_wgrad_recompute_kernel   conv a third time for xhat at every position of the BatchNorm backward.
 // EPI 0 is the storing form (eval-mode forward, tests).
 #define C1_TPW 8
-#define C1_MIN_GAMMA 1e-2f        // == BN_INV_MIN_GAMMA (bn_pool.hip): below it xhat is not recoverable from the pooled output
 #define C1H_COPY 1200             // halves per shifted copy [3][20][20]
 #define C1H_IMG (4 * C1H_COPY)    // halves per halo image (four copies): 9600 B (+ 16 B: the dump slot of C1Halo::stash)
 #define C1H_IMG_ALLOC (C1H_IMG + 8)
@@ -228,14 +228,14 @@ __global__ __launch_bounds__(256) void conv3d_c1_fwd_mfma_kernel(const float* __
   float sc[4] = {0.f, 0.f, 0.f, 0.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (EPI == 1) {
     if (y != nullptr)
-      for (int c = 0; c < 16; ++c) store |= fabsf(ep.gamma[c]) < C1_MIN_GAMMA;      // uniform over the grid
+      for (int c = 0; c < 16; ++c) store |= fabsf(ep.gamma[c]) < BN_INV_MIN_GAMMA;      // uniform over the grid
   }
   if constexpr (EPI == 2) {
-    // the expressions of bn_pool_act_fwd_kernel, channels 4 g .. 4 g + 3
+    // channels 4 g .. 4 g + 3
     const float4 ga = *reinterpret_cast<const float4*>(ep.gamma + 4 * g), is = *reinterpret_cast<const float4*>(ep.invstd + 4 * g);
     const float4 be = *reinterpret_cast<const float4*>(ep.beta + 4 * g), mu = *reinterpret_cast<const float4*>(ep.mean + 4 * g);
-    sc[0] = ga.x * is.x; sc[1] = ga.y * is.y; sc[2] = ga.z * is.z; sc[3] = ga.w * is.w;
-    sh[0] = be.x - mu.x * sc[0]; sh[1] = be.y - mu.y * sc[1]; sh[2] = be.z - mu.z * sc[2]; sh[3] = be.w - mu.w * sc[3];
+    bn_scale_shift(ga.x, is.x, be.x, mu.x, sc[0], sh[0]); bn_scale_shift(ga.y, is.y, be.y, mu.y, sc[1], sh[1]);
+    bn_scale_shift(ga.z, is.z, be.z, mu.z, sc[2], sh[2]); bn_scale_shift(ga.w, is.w, be.w, mu.w, sc[3], sh[3]);
   }
   for (int kt = 0; kt < ntile; ++kt) {
     const int bt = (int)cbt, x0 = (int)ctx * 16, y0 = (int)cty * 16;
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_fwd_mfma_kernel(const float* __
       for (int k = 0; k < 2; ++k)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float va = acc[k][r] * sc[r] + sh[r], vb = acc[2 + k][r] * sc[r] + sh[r];
+          const float va = bn_affine(acc[k][r], sc[r], sh[r]), vb = bn_affine(acc[2 + k][r], sc[r], sh[r]);
           own[k][r] = odd ? vb : va;
           rcv[k][r] = dpp_f32<0xB1, 0xf>(odd ? va : vb, 0.f);                       // quad_perm [1,0,3,2]: the pair partner's value
         }
@@ -281,11 +281,11 @@ __global__ __launch_bounds__(256) void conv3d_c1_fwd_mfma_kernel(const float* __
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const float v = (dx == 1) == odd ? own[dy][r] : rcv[dy][r];
-              if (v > best[r] || (v != v && best[r] == best[r])) { best[r] = v; bi[r] = dy * 2 + dx; }
+              if (pool_take(v, best[r])) { best[r] = v; bi[r] = dy * 2 + dx; }
             }
         float a4[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) a4[r] = best[r] > 0.f ? best[r] : 0.01f * best[r];
+        for (int r = 0; r < 4; ++r) a4[r] = leaky_fwd(best[r]);
         const int64_t pp = (((int64_t)bt * ep.Hp + py) * ep.Wp + px) * 16 + 4 * g;
         *reinterpret_cast<float4*>(ep.out + pp) = make_float4(a4[0], a4[1], a4[2], a4[3]);
         if (ep.out16 != nullptr) *reinterpret_cast<uint2*>(ep.out16 + pp) = make_uint2(pack2<2>(a4[0], a4[1]), pack2<2>(a4[2], a4[3]));
@@ -331,13 +331,9 @@ struct C1BnArgs {
   const float* beta;            // recompute kernel only: the sign of the pooled output is re-derived from the recomputed y
   int pool, Hp, Wp;
 };
-// The gradient on the way into the weight-gradient product, in two steps -- the same arithmetic as bn_pool_act_bwd_dx_kernel (bn_pool.hip),
-// expression for expression, per channel (a form that takes the four channels or the gg array compiles to other code).
-// LeakyReLU(0.01) + max pool: the pooled gradient dv, for the window position that is the channel's argmax (else 0: the caller's test), times
-// the activation's slope; s decides the sign of the pooled output (the output itself, or the pre-activation it is recomputed from).
-__device__ __forceinline__ float c1_pool_grad(float dv, float s) { return dv * (s > 0.f ? 1.f : 0.01f); }
-// BatchNorm backward of the conv output y: k0 = gamma invstd, k1 = mean(dz), k2 = mean(dz xhat)
-__device__ __forceinline__ float c1_bn_bwd(float gg, float y, float mu, float is, float k0, float k1, float k2) { return k0 * (gg - k1 - (y - mu) * is * k2); }
+// The gradient on the way into the weight-gradient product, in the two steps of bn_pool_act_bwd_dx_kernel and with its scalars (bn_act.h), per
+// channel.  LeakyReLU(0.01) + max pool: the pooled gradient dv, for the window position that is the channel's argmax (else 0), times
+// leaky_slope of the pooled output (or of the pre-activation it is recomputed from: the same sign).  Then bn_dy on the conv output y.
 
 // dW[16][75] partial per block; dy tile and x halo in LDS.  Thread = ((kd,kh) pair, 4-channel group, row worker): it walks
 // rows of the 16x16 tile keeping the five x values of the kw window in registers (one new LDS value per position) and
@@ -387,19 +383,19 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_kernel(const float* __res
             const uchar4 am = *reinterpret_cast<const uchar4*>(bn.argmax + pp);
             if (am.x == here || am.y == here || am.z == here || am.w == here) {
               const float4 dv = *reinterpret_cast<const float4*>(bn.dout + pp), ov = *reinterpret_cast<const float4*>(bn.out + pp);
-              if (am.x == here) gg[0] = c1_pool_grad(dv.x, ov.x);
-              if (am.y == here) gg[1] = c1_pool_grad(dv.y, ov.y);
-              if (am.z == here) gg[2] = c1_pool_grad(dv.z, ov.z);
-              if (am.w == here) gg[3] = c1_pool_grad(dv.w, ov.w);
+              if (am.x == here) gg[0] = dv.x * leaky_slope(ov.x);
+              if (am.y == here) gg[1] = dv.y * leaky_slope(ov.y);
+              if (am.z == here) gg[2] = dv.z * leaky_slope(ov.z);
+              if (am.w == here) gg[3] = dv.w * leaky_slope(ov.w);
             }
           }
           const float4 mu = *reinterpret_cast<const float4*>(bn.mean + cc), is = *reinterpret_cast<const float4*>(bn.invstd + cc);
           const float4 k0 = *reinterpret_cast<const float4*>(bn.coef + cc), k1 = *reinterpret_cast<const float4*>(bn.coef + 16 + cc);
           const float4 k2 = *reinterpret_cast<const float4*>(bn.coef + 32 + cc);
-          v.x = c1_bn_bwd(gg[0], v.x, mu.x, is.x, k0.x, k1.x, k2.x);
-          v.y = c1_bn_bwd(gg[1], v.y, mu.y, is.y, k0.y, k1.y, k2.y);
-          v.z = c1_bn_bwd(gg[2], v.z, mu.z, is.z, k0.z, k1.z, k2.z);
-          v.w = c1_bn_bwd(gg[3], v.w, mu.w, is.w, k0.w, k1.w, k2.w);
+          v.x = bn_dy(gg[0], v.x, mu.x, is.x, k0.x, k1.x, k2.x);
+          v.y = bn_dy(gg[1], v.y, mu.y, is.y, k0.y, k1.y, k2.y);
+          v.z = bn_dy(gg[2], v.z, mu.z, is.z, k0.z, k1.z, k2.z);
+          v.w = bn_dy(gg[3], v.w, mu.w, is.w, k0.w, k1.w, k2.w);
         }
       }
       *reinterpret_cast<float4*>(&dys[pos][cc]) = v;
@@ -501,18 +497,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         float gg[4] = {0.f, 0.f, 0.f, 0.f};
         if (py < bn.Hp && px < bn.Wp) {
           const int here = (oy - py * bn.pool) * bn.pool + (ox - px * bn.pool);
-          if (am[it].x == here) gg[0] = c1_pool_grad(dv[it].x, ov[it].x);
-          if (am[it].y == here) gg[1] = c1_pool_grad(dv[it].y, ov[it].y);
-          if (am[it].z == here) gg[2] = c1_pool_grad(dv[it].z, ov[it].z);
-          if (am[it].w == here) gg[3] = c1_pool_grad(dv[it].w, ov[it].w);
+          if (am[it].x == here) gg[0] = dv[it].x * leaky_slope(ov[it].x);
+          if (am[it].y == here) gg[1] = dv[it].y * leaky_slope(ov[it].y);
+          if (am[it].z == here) gg[2] = dv[it].z * leaky_slope(ov[it].z);
+          if (am[it].w == here) gg[3] = dv[it].w * leaky_slope(ov[it].w);
         }
         const float4 mu = *reinterpret_cast<const float4*>(bn.mean + cc), is = *reinterpret_cast<const float4*>(bn.invstd + cc);
         const float4 k0 = *reinterpret_cast<const float4*>(bn.coef + cc), k1 = *reinterpret_cast<const float4*>(bn.coef + 16 + cc);
         const float4 k2 = *reinterpret_cast<const float4*>(bn.coef + 32 + cc);
-        v.x = c1_bn_bwd(gg[0], yv[it].x, mu.x, is.x, k0.x, k1.x, k2.x);
-        v.y = c1_bn_bwd(gg[1], yv[it].y, mu.y, is.y, k0.y, k1.y, k2.y);
-        v.z = c1_bn_bwd(gg[2], yv[it].z, mu.z, is.z, k0.z, k1.z, k2.z);
-        v.w = c1_bn_bwd(gg[3], yv[it].w, mu.w, is.w, k0.w, k1.w, k2.w);
+        v.x = bn_dy(gg[0], yv[it].x, mu.x, is.x, k0.x, k1.x, k2.x);
+        v.y = bn_dy(gg[1], yv[it].y, mu.y, is.y, k0.y, k1.y, k2.y);
+        v.z = bn_dy(gg[2], yv[it].z, mu.z, is.z, k0.z, k1.z, k2.z);
+        v.w = bn_dy(gg[3], yv[it].w, mu.w, is.w, k0.w, k1.w, k2.w);
       }
       dyT[(cc + 0) * DYS + pos] = f2bf(v.x);
       dyT[(cc + 1) * DYS + pos] = f2bf(v.y);
@@ -587,7 +583,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
   if (tid < 16) {
     const float m_ = bn.mean[tid], c0_ = bn.coef[tid];
     cst[0][tid] = m_; cst[1][tid] = bn.invstd[tid]; cst[2][tid] = c0_; cst[3][tid] = bn.coef[16 + tid]; cst[4][tid] = bn.coef[32 + tid];
-    cst[5][tid] = bn.beta[tid] - m_ * c0_;
+    cst[5][tid] = bn_shift(bn.beta[tid], m_, c0_);
   }
   f32x4 acc[5];
 #pragma unroll
@@ -643,17 +639,17 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
         float gg[4] = {0.f, 0.f, 0.f, 0.f};
         if (py < bn.Hp && px < bn.Wp) {
           const int here = (oy - py * bn.pool) * bn.pool + (ox - px * bn.pool);
-          // the pooled output is positive exactly when the forward's pre-activation at the argmax was: y * (gamma invstd) + (beta - mean gamma invstd),
-          // the expression of conv3d_c1_fwd_mfma_kernel<2> on the same recomputed y -- `out` is not read
-          if (am[i].x == here) gg[0] = c1_pool_grad(dv[i].x, z[i][0] * k0.x + sh.x);
-          if (am[i].y == here) gg[1] = c1_pool_grad(dv[i].y, z[i][1] * k0.y + sh.y);
-          if (am[i].z == here) gg[2] = c1_pool_grad(dv[i].z, z[i][2] * k0.z + sh.z);
-          if (am[i].w == here) gg[3] = c1_pool_grad(dv[i].w, z[i][3] * k0.w + sh.w);
+          // the pooled output is positive exactly when the forward's pre-activation at the argmax was: bn_affine with (gamma invstd,
+          // beta - mean gamma invstd), as conv3d_c1_fwd_mfma_kernel<2> formed it on the same recomputed y -- `out` is not read
+          if (am[i].x == here) gg[0] = dv[i].x * leaky_slope(bn_affine(z[i][0], k0.x, sh.x));
+          if (am[i].y == here) gg[1] = dv[i].y * leaky_slope(bn_affine(z[i][1], k0.y, sh.y));
+          if (am[i].z == here) gg[2] = dv[i].z * leaky_slope(bn_affine(z[i][2], k0.z, sh.z));
+          if (am[i].w == here) gg[3] = dv[i].w * leaky_slope(bn_affine(z[i][3], k0.w, sh.w));
         }
-        v.x = c1_bn_bwd(gg[0], z[i][0], mu.x, is.x, k0.x, k1.x, k2.x);
-        v.y = c1_bn_bwd(gg[1], z[i][1], mu.y, is.y, k0.y, k1.y, k2.y);
-        v.z = c1_bn_bwd(gg[2], z[i][2], mu.z, is.z, k0.z, k1.z, k2.z);
-        v.w = c1_bn_bwd(gg[3], z[i][3], mu.w, is.w, k0.w, k1.w, k2.w);
+        v.x = bn_dy(gg[0], z[i][0], mu.x, is.x, k0.x, k1.x, k2.x);
+        v.y = bn_dy(gg[1], z[i][1], mu.y, is.y, k0.y, k1.y, k2.y);
+        v.z = bn_dy(gg[2], z[i][2], mu.z, is.z, k0.z, k1.z, k2.z);
+        v.w = bn_dy(gg[3], z[i][3], mu.w, is.w, k0.w, k1.w, k2.w);
       }
       dyT[(4 * g + 0) * DYS + pos] = f2bf(v.x);
       dyT[(4 * g + 1) * DYS + pos] = f2bf(v.y);

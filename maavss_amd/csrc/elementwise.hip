@@ -4,12 +4,13 @@
 //   adam_step    torch.optim.Adam (train_avse_frames.py:92,180; betas .9/.999, eps 1e-8, no weight decay) over
 //                one flat f32 parameter buffer (multi-tensor by construction: all parameters live in one buffer)
 #include "common.h"
+#include "bn_act.h"      // tanh_slope, sigmoid_slope
 
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ out,
                                                       float* __restrict__ dz, int64_t n, int act) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float o = out[i];
-    dz[i] = dout[i] * (act == 1 ? 1.f - o * o : o * (1.f - o));
+    dz[i] = dout[i] * (act == 1 ? tanh_slope(o) : sigmoid_slope(o));
   }
 }
 

@@ -9,6 +9,7 @@
 // Small-M problems (M = batch) are weight-streaming, HBM-bound: the launcher swaps the operands so the
 // weight is the M side, picks a narrow N tile and splits K across blocks (f32 atomics).
 #include "mma.h"
+#include "bn_act.h"      // dense_act
 
 struct GemmArgs {
   const float* A;
@@ -20,12 +21,6 @@ struct GemmArgs {
   float alpha;
   int beta, act, split_k, k_per_split;
 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-  if (act == 1) return tanhf(v);
-  if (act == 2) return 1.0f / (1.0f + __expf(-v));
-  return v;
-}
 
 // Loads a [ROWS x 32] operand tile into registers (NV float4 per thread, zero-filled out of range).
 template <int ROWS>
@@ -145,23 +140,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
             atomicAdd(c, v);
           } else {
             if (g.beta) v += *c;
-            *c = apply_act(v, g.act);
+            *c = dense_act(v, g.act);
           }
         }
       }
-}
-
-__global__ void gemm_zero_kernel(float* C, int64_t ldc, int rows, int cols) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)rows * cols;
-       i += (int64_t)gridDim.x * blockDim.x)
-    C[(i / cols) * ldc + (i % cols)] = 0.f;
-}
-__global__ void gemm_act_kernel(float* C, int64_t ldc, int rows, int cols, int act) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)rows * cols;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float* c = C + (i / cols) * ldc + (i % cols);
-    *c = apply_act(*c, act);
-  }
 }
 
 template <int PRECISE>
@@ -180,6 +162,9 @@ static void launch_gemm(GemmArgs g, int cfg, hipStream_t st) {
 
 int maavss_linear_skinny_try(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB, float* C, int64_t ldc,
                              int transC, int64_t M, int64_t N, int64_t K, float alpha, int beta, int act, hipStream_t st, int* taken);
+// the zero pass before and the activation pass after a product split with atomics (linear_skinny.hip)
+int maavss_dense_zero(float* C, int64_t ldc, int rows, int cols, hipStream_t st);
+int maavss_dense_act(float* C, int64_t ldc, int rows, int cols, int act, hipStream_t st);
 
 extern "C" int maavss_gemm_f32(const float* A, int64_t lda, int transA, const float* B, int64_t ldb, int transB,
                                float* C, int64_t ldc, int transC, int64_t M, int64_t N, int64_t K, float alpha,
@@ -228,18 +213,12 @@ extern "C" int maavss_gemm_f32(const float* A, int64_t lda, int transA, const fl
   g.split_k = split_k;
   g.k_per_split = kps;
   const int rows = g.transC ? g.N : g.M, cols = g.transC ? g.M : g.N;
-  if (split_k > 1 && !beta) {
-    hipLaunchKernelGGL(gemm_zero_kernel, dim3(min(2048, cdiv((int64_t)rows * cols, 256))), dim3(256), 0, st, C, ldc,
-                       rows, cols);
-  }
+  if (split_k > 1 && !beta)
+    if (int rc = maavss_dense_zero(C, ldc, rows, cols, st)) return rc;
   if (precise == MODE_F32) launch_gemm<MODE_F32>(g, cfg, st);
   else if (precise == MODE_F16) launch_gemm<MODE_F16>(g, cfg, st);
   else launch_gemm<MODE_BF16>(g, cfg, st);
   MAAVSS_LAUNCH_CHECK("gemm_kernel");
-  if (split_k > 1 && act != 0) {
-    hipLaunchKernelGGL(gemm_act_kernel, dim3(min(2048, cdiv((int64_t)rows * cols, 256))), dim3(256), 0, st, C, ldc,
-                       rows, cols, act);
-    MAAVSS_LAUNCH_CHECK("gemm_act_kernel");
-  }
+  if (split_k > 1 && act != 0) return maavss_dense_act(C, ldc, rows, cols, act, st);
   return MAAVSS_OK;
 }

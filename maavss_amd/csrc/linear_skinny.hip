@@ -11,6 +11,7 @@
 // {e, 4 + e, 8 + e, 12 + e} -- so operands are loaded 16 bytes per lane and no shuffle is needed (any split of K over the MFMAs
 // is valid as long as both operands use the same one).
 #include "mma.h"
+#include "bn_act.h"      // dense_act
 
 #define LS_KS 512          // fwd: K slice per workgroup (X slice [32][LS_KS] in LDS)
 #define LS_NS 512          // dx: N slice per workgroup (64 rows per wave)
@@ -27,11 +28,6 @@ struct LinArgs {
   float* part;               // atomic == 2: [slices][32][cols]
 };
 
-__device__ __forceinline__ float ls_act(float v, int a) {
-  if (a == 1) return tanhf(v);
-  if (a == 2) return 1.0f / (1.0f + __expf(-v));
-  return v;
-}
 __device__ __forceinline__ void ls_mfma(f32x4& acc, float a, float b) { acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
 
 // ---- fwd: grid (ceil(N / 128), ceil(K / LS_KS)), 512 threads
@@ -86,7 +82,7 @@ __global__ __launch_bounds__(512) void linear_fwd_skinny_kernel(LinArgs g) {
           atomicAdd(c, v);
         } else {
           if (g.beta) v += *c;
-          *c = ls_act(v, g.actfn);
+          *c = dense_act(v, g.actfn);
         }
       }
     }
@@ -157,7 +153,7 @@ __global__ __launch_bounds__(512) void linear_dx_skinny_kernel(LinArgs g) {
         atomicAdd(c, v.x); atomicAdd(c + 1, v.y); atomicAdd(c + 2, v.z); atomicAdd(c + 3, v.w);
       } else {
         if (g.beta) { const float4 o = *reinterpret_cast<const float4*>(c); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-        *reinterpret_cast<float4*>(c) = make_float4(ls_act(v.x, g.actfn), ls_act(v.y, g.actfn), ls_act(v.z, g.actfn), ls_act(v.w, g.actfn));
+        *reinterpret_cast<float4*>(c) = make_float4(dense_act(v.x, g.actfn), dense_act(v.y, g.actfn), dense_act(v.z, g.actfn), dense_act(v.w, g.actfn));
       }
     }
   }
@@ -209,6 +205,7 @@ __global__ __launch_bounds__(256) void linear_dw_skinny_kernel(LinArgs g) {   //
   }
 }
 
+// the zero pass before and the activation pass after a product split with atomics; also gemm.hip's, through maavss_dense_zero / maavss_dense_act
 __global__ void linear_zero_kernel(float* C, int64_t ldc, int rows, int cols) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)rows * cols; i += (int64_t)gridDim.x * blockDim.x)
     C[(i / cols) * ldc + (i % cols)] = 0.f;
@@ -216,7 +213,7 @@ __global__ void linear_zero_kernel(float* C, int64_t ldc, int rows, int cols) {
 __global__ void linear_act_kernel(float* C, int64_t ldc, int rows, int cols, int act) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)rows * cols; i += (int64_t)gridDim.x * blockDim.x) {
     float* c = C + (i / cols) * ldc + (i % cols);
-    *c = ls_act(*c, act);
+    *c = dense_act(*c, act);
   }
 }
 
@@ -227,12 +224,40 @@ __global__ void linear_reduce_kernel(const float* __restrict__ part, int slices,
     float* c = C + (int64_t)m * ldc + n;
     float v = beta ? *c : 0.f;
     for (int s = 0; s < slices; ++s) v += part[((int64_t)s * 32 + m) * cols + n];
-    *c = ls_act(v, act);
+    *c = dense_act(v, act);
   }
 }
 
 static int ls_blocks(int64_t elems) { const int b = cdiv(elems, 256); return b < 2048 ? b : 2048; }
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int maavss_dense_zero(float* C, int64_t ldc, int rows, int cols, hipStream_t st) {
+  hipLaunchKernelGGL(linear_zero_kernel, dim3(ls_blocks((int64_t)rows * cols)), dim3(256), 0, st, C, ldc, rows, cols);
+  MAAVSS_LAUNCH_CHECK("linear_zero_kernel");
+  return MAAVSS_OK;
+}
+int maavss_dense_act(float* C, int64_t ldc, int rows, int cols, int act, hipStream_t st) {
+  hipLaunchKernelGGL(linear_act_kernel, dim3(ls_blocks((int64_t)rows * cols)), dim3(256), 0, st, C, ldc, rows, cols, act);
+  MAAVSS_LAUNCH_CHECK("linear_act_kernel");
+  return MAAVSS_OK;
+}
+
+// The fwd or dx kernel over `slices` slices of its reduction, [g.Mb][cols] outputs.  One slice: the kernel finishes the output itself.
+// Atomic slices: zero pass (unless beta), kernel, activation pass.  Deterministic slices: partial sums into det_ws, added in slice order.
+static int ls_launch_sliced(void (*kern)(LinArgs), const char* name, int grid_x, int slices, int cols, bool det, float* det_ws, LinArgs g, hipStream_t st) {
+  g.atomic = slices > 1 ? (det ? 2 : 1) : 0;
+  g.part = det_ws;
+  if (g.atomic == 1 && !g.beta)
+    if (int rc = maavss_dense_zero(g.out, g.ld_out, g.Mb, cols, st)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid_x, slices), dim3(512), 0, st, g);
+  MAAVSS_LAUNCH_CHECK(name);
+  if (g.atomic == 1 && g.actfn) return maavss_dense_act(g.out, g.ld_out, g.Mb, cols, g.actfn, st);
+  if (g.atomic == 2) {
+    hipLaunchKernelGGL(linear_reduce_kernel, dim3(ls_blocks((int64_t)g.Mb * cols)), dim3(256), 0, st, det_ws, slices, g.out, g.ld_out, g.Mb, cols, g.beta, g.actfn);
+    MAAVSS_LAUNCH_CHECK("linear_reduce_kernel");
+  }
+  return MAAVSS_OK;
+}
 
 // Called by maavss_gemm_f32 (gemm.hip) for its exact-f32 mode.  *taken = 1 if one of the three forms took the problem, 0 if the
 // generic kernel has to (shape / alignment outside what they cover); returns a status code.
@@ -251,30 +276,14 @@ int maavss_linear_skinny_try(const float* A, int64_t lda, int transA, const floa
       aligned16(A) && aligned16(B) && aligned16(C)) {
     // fwd: C[M][N] = A[M][K] . B[N][K]^T
     g.act = A; g.ld_act = lda; g.w = B; g.ld_w = ldb; g.out = C; g.ld_out = ldc; g.Mb = (int)M; g.N = (int)N; g.K = (int)K;
-    const int slices = cdiv(K, LS_KS);
-    g.atomic = slices > 1 ? (det ? 2 : 1) : 0;
-    g.part = det_ws;
-    if (g.atomic == 1 && !beta) hipLaunchKernelGGL(linear_zero_kernel, dim3(ls_blocks(M * N)), dim3(256), 0, st, C, ldc, (int)M, (int)N);
-    hipLaunchKernelGGL(linear_fwd_skinny_kernel, dim3(cdiv(N, 128), slices), dim3(512), 0, st, g);
-    if (g.atomic == 1 && act) hipLaunchKernelGGL(linear_act_kernel, dim3(ls_blocks(M * N)), dim3(256), 0, st, C, ldc, (int)M, (int)N, act);
-    if (g.atomic == 2) hipLaunchKernelGGL(linear_reduce_kernel, dim3(ls_blocks(M * N)), dim3(256), 0, st, det_ws, slices, C, ldc, (int)M, (int)N, beta, act);
-    MAAVSS_LAUNCH_CHECK("linear_fwd_skinny_kernel");
     *taken = 1;
-    return MAAVSS_OK;
+    return ls_launch_sliced(linear_fwd_skinny_kernel, "linear_fwd_skinny_kernel", cdiv(N, 128), cdiv(K, LS_KS), (int)N, det, det_ws, g, st);
   }
   if (!transA && transB && det_ok(K, LS_NS, N) && M <= 32 && N >= 256 && N % 4 == 0 && K >= LS_NS && ldb % 4 == 0 && ldc % 4 == 0 && aligned16(B) && aligned16(C)) {
     // dx: C[M][N] = A[M][K] . B[K][N]   (B = the weight [K rows][N columns]; K is the reduction)
     g.act = A; g.ld_act = lda; g.w = B; g.ld_w = ldb; g.out = C; g.ld_out = ldc; g.Mb = (int)M; g.N = (int)K; g.K = (int)N;
-    const int slices = cdiv(K, LS_NS);
-    g.atomic = slices > 1 ? (det ? 2 : 1) : 0;
-    g.part = det_ws;
-    if (g.atomic == 1 && !beta) hipLaunchKernelGGL(linear_zero_kernel, dim3(ls_blocks(M * N)), dim3(256), 0, st, C, ldc, (int)M, (int)N);
-    hipLaunchKernelGGL(linear_dx_skinny_kernel, dim3(cdiv(N, 64), slices), dim3(512), 0, st, g);
-    if (g.atomic == 1 && act) hipLaunchKernelGGL(linear_act_kernel, dim3(ls_blocks(M * N)), dim3(256), 0, st, C, ldc, (int)M, (int)N, act);
-    if (g.atomic == 2) hipLaunchKernelGGL(linear_reduce_kernel, dim3(ls_blocks(M * N)), dim3(256), 0, st, det_ws, slices, C, ldc, (int)M, (int)N, beta, act);
-    MAAVSS_LAUNCH_CHECK("linear_dx_skinny_kernel");
     *taken = 1;
-    return MAAVSS_OK;
+    return ls_launch_sliced(linear_dx_skinny_kernel, "linear_dx_skinny_kernel", cdiv(N, 64), cdiv(K, LS_NS), (int)N, det, det_ws, g, st);
   }
   if (transA && transB && K <= 32 && M >= 256 && N >= 256 && N % 4 == 0 && ldc % 4 == 0 && aligned16(C) && act == 0) {
     // dw: C[M][N] = A[K][M]^T . B[K][N]   (A = dY [batch][M], B = X [batch][N])

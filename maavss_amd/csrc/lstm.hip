@@ -13,12 +13,11 @@
 //   gs   [B][L][2][4][H]   post-activation gates i,f,g,o
 //   cs   [B][L][2][H]      cell state after step t
 #include "common.h"
+#include "bn_act.h"      // sigmoid_fast: the sigmoid of the dense activation
 
 #define LH 256
 #define JT 8
 #define BB 32
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
 
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restrict__ gx, const float* __restrict__ whh_f,
                                                             const float* __restrict__ whh_b, float* __restrict__ av,
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(const float* __restr
     if (b < B) {
       const float* gxp = gx + (((int64_t)b * L + t) * 2 + d) * 4 * LH;
       a0 += gxp[j]; a1 += gxp[LH + j]; a2 += gxp[2 * LH + j]; a3 += gxp[3 * LH + j];
-      const float ig = sigmoidf_(a0), fg = sigmoidf_(a1), gg = tanhf(a2), og = sigmoidf_(a3);
+      const float ig = sigmoid_fast(a0), fg = sigmoid_fast(a1), gg = tanhf(a2), og = sigmoid_fast(a3);
       const int64_t ci = (((int64_t)b * L + t) * 2 + d) * LH + j;
       const float cprev = first ? 0.f : cs[(((int64_t)b * L + tprev) * 2 + d) * LH + j];
       const float c = fg * cprev + ig * gg;
