@@ -1,11 +1,12 @@
 // The first Conv3d(3,5,5) layer of the visual encoder (C_in = 1, C_out = 16, K = 75; reference avse_model_final.py:34): forward and weight
 // gradient (the network input needs no gradient).  x [BT][H][W] is the reference's NCDHW input as is, y [BT][H][W][16] channels-last.
 // The shipped 16-bit path runs on the matrix pipe and never stores the conv output: conv3d_c1_fwd_mfma_kernel<1> (conv -> BatchNorm partial
-// sums), <2> (conv again -> BatchNorm, 2x2 max pool, LeakyReLU) and conv3d_c1_wgrad_recompute_kernel (conv a third time inside the fused
+// sums), <2> (conv again -> BatchNorm, 2x2 max pool, LeakyReLU) and conv3d_c1_wgrad_mfma_kernel<true> (conv a third time inside the fused
 // BatchNorm / pool / activation backward and weight gradient).  With a stored conv output: conv3d_c1_fwd_mfma_kernel<0> (eval-mode forward) and
-// conv3d_c1_wgrad_mfma_kernel (the fused weight gradient from y).  precise=True: conv3d_c1_prep_kernel, conv3d_c1_fwd_kernel and
-// conv3d_c1_wgrad_kernel<false|true>, an exact-f32 direct convolution on the VALU from an LDS halo tile, weights as wave-uniform scalar operands.
-// The per-chunk partials of all three weight-gradient kernels are summed by conv3d_c1_wgrad_reduce_kernel (conv3d_wgrad.hip).
+// conv3d_c1_wgrad_mfma_kernel<false> (the same kernel body, y read instead of recomputed).  precise=True: conv3d_c1_prep_kernel,
+// conv3d_c1_fwd_kernel and conv3d_c1_wgrad_kernel<false|true>, an exact-f32 direct convolution on the VALU from an LDS halo tile, weights as
+// wave-uniform scalar operands.  The per-chunk partials of both weight-gradient kernels are summed by conv3d_c1_wgrad_reduce_kernel
+// (conv3d_wgrad.hip).
 #include "conv3d_tile.h"
 #include "bn_act.h"      // the BatchNorm / pool / LeakyReLU scalars this file shares with bn_pool.hip
 
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_fwd_kernel(const float* __restr
 //   EPI 2  (conv3d_c1_bn_pool_act)  conv again -> gamma (y - mean) invstd + beta -> 2x2 max pool -> LeakyReLU: the pooled
 //                                   activation (f32 + IEEE half) and the argmax byte, bit-identical to bn_pool_act_fwd_kernel on
 //                                   the stored y (the scalars of bn_act.h in the same scan order dy, dx);
-//   conv3d_c1_wgrad_recompute_kernel   conv a third time for xhat at every position of the BatchNorm backward.
+//   conv3d_c1_wgrad_mfma_kernel<true>  conv a third time for xhat at every position of the BatchNorm backward.
 // EPI 0 is the storing form (eval-mode forward, tests).
 #define C1_TPW 8
 #define C1H_COPY 1200             // halves per shifted copy [3][20][20]
@@ -331,10 +332,6 @@ struct C1BnArgs {
   const float* beta;            // recompute kernel only: the sign of the pooled output is re-derived from the recomputed y
   int pool, Hp, Wp;
 };
-// The gradient on the way into the weight-gradient product, in the two steps of bn_pool_act_bwd_dx_kernel and with its scalars (bn_act.h), per
-// channel.  LeakyReLU(0.01) + max pool: the pooled gradient dv, for the window position that is the channel's argmax (else 0), times
-// leaky_slope of the pooled output (or of the pre-activation it is recomputed from: the same sign).  Then bn_dy on the conv output y.
-
 // dW[16][75] partial per block; dy tile and x halo in LDS.  Thread = ((kd,kh) pair, 4-channel group, row worker): it walks
 // rows of the 16x16 tile keeping the five x values of the kw window in registers (one new LDS value per position) and
 // reading its 4 dy channels once per position -- 20 FMAs per 2 LDS reads.  (The first version, one thread per tap
@@ -436,135 +433,41 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_kernel(const float* __res
 // The first layer's weight gradient on the matrix pipe (16-bit path), BatchNorm / max-pool / LeakyReLU backward fused as in
 // conv3d_c1_wgrad_kernel<true>:  dW[tap][co] = sum over positions of x[pos + tap] * dy[pos][co]  as an MFMA product with the
 // 75 taps as rows (5 tiles of 16, the last 5 rows unused), co as columns and the POSITION as the K dimension (32 positions =
-// two tile rows per step).  Per 16x16 tile: the x halo is staged as bf16 [3][20][24]; dy is formed in f32 from the pooled
-// gradient exactly as before, rounded to bf16 and stored TRANSPOSED [co][pos] so that a B fragment (8 consecutive positions
-// of one channel) is one 16-byte LDS read; an A fragment of lane (tap, k group) is 8 consecutive halo columns of the tap's
-// (kd, kh) row starting at column kw (eight 16-bit reads).  A wave takes 2 of the tile's 8 K-steps for all 5 tap tiles and
-// keeps its 5 accumulators across the chunk's tiles; the waves are summed once per chunk.  75 FMAs per (position, channel)
-// on the VALU become 5 MFMAs per 32 positions: the f32 kernel took 1.55 ms per step, this one is bound by reading y (1.6 GB).
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv3d_c1_wgrad_mfma_kernel(const float* __restrict__ x, const float* __restrict__ yconv,
+// two tile rows per step).  A wave takes 2 of the tile's 8 K-steps for all 5 tap tiles and keeps its 5 accumulators across the
+// chunk's tiles; the waves are summed once per chunk.  75 FMAs per (position, channel) on the VALU become 5 MFMAs per 32 positions.
+// The gradient on the way into the product is formed in the two steps of bn_pool_act_bwd_dx_kernel and with its scalars (bn_act.h),
+// per channel.  LeakyReLU(0.01) + max pool: the pooled gradient dv, for the window position that is the channel's argmax (else 0),
+// times leaky_slope of the pooled output (or of the pre-activation it is recomputed from: the same sign).  Then bn_dy on the conv
+// output y.  It is rounded to bf16 and stored TRANSPOSED [co][pos], so that a B fragment (8 consecutive positions of one channel)
+// is one 16-byte LDS read.
+// RECOMPUTE = false: `src` is the stored conv output y (bound by reading it: 1.6 GB at the benched shape), the sign comes from
+// bn.out.  RECOMPUTE = true: `src` is the layer's weights and the tile's y is recomputed from the halo that is staged anyway (C1Conv on
+// an IEEE-half image of it: the arithmetic of conv3d_c1_fwd_mfma_kernel, so xhat is bit-identical to what the forward normalised).
+// The MFMA result layout of that conv -- lane (column l16, channel group g) holds channels 4 g .. 4 g + 3 of the positions
+// (row 4 wv + i, l16) -- is the dy-formation mapping of both forms: each lane forms its 4 x 4 values from registers (of y: a float4
+// load per position, 1 KiB contiguous per wave and row) and writes them transposed.
+// The bf16 halo of the weight-gradient product is kept in the four-shifted-copies form of the forward: the A fragment of lane
+// (tap, k group) is 8 consecutive columns starting at kw + 8 (g & 1), i.e. copy kw & 3 at an 8-byte aligned column -- one
+// ds_read2_b64 instead of the eight 16-bit reads and four packs a single [3][20][24] image takes.  The images are double-buffered
+// and the next tile's halo is fetched a tile ahead.
+template <bool RECOMPUTE>
+__global__ __launch_bounds__(256) void conv3d_c1_wgrad_mfma_kernel(const float* __restrict__ x, const float* __restrict__ src,
                                                                    float* __restrict__ partials, int T, int H, int W, int tiles_x,
                                                                    int tiles_y, int BT, int tiles_per_chunk, int nchunk, C1BnArgs bn) {
   constexpr int DYS = 256 + 8;                                        // dyT row stride (elements): 528 B, 16-byte aligned
-  __shared__ __attribute__((aligned(16))) char smem[4 * 80 * 16 * 4];  // max(halo + dyT = 2880 + 8448 B, final reduction 20480 B)
-  unsigned short (*halo)[20][24] = reinterpret_cast<unsigned short (*)[20][24]>(smem);
-  unsigned short* dyT = reinterpret_cast<unsigned short*>(smem + 3 * 20 * 24 * 2);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l16 = lane & 15, g = lane >> 4;
-  const int tiles_total = BT * tiles_x * tiles_y;
-  const int chunk = xcd_chunk(nchunk);
-  if (chunk >= nchunk) return;
-  // per-lane halo byte offsets of the 5 tap tiles: tap (kd, kh, kw), plus this lane's k group (row g >> 1, column 8 (g & 1))
-  int abase[5];
-#pragma unroll
-  for (int mt = 0; mt < 5; ++mt) {
-    int tap = 16 * mt + l16;
-    tap = tap < 75 ? tap : 74;                                       // rows 75..79 of the last tile: computed, never stored
-    const int kd = tap / 25, kh = (tap % 25) / 5, kw = tap % 5;
-    abase[mt] = (((kd * 20 + kh + (g >> 1)) * 24) + kw + 8 * (g & 1)) * 2;
-  }
-  f32x4 acc[5];
-#pragma unroll
-  for (int mt = 0; mt < 5; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int tile_beg = chunk * tiles_per_chunk, tile_end = min(tiles_total, tile_beg + tiles_per_chunk);
-  for (int tile = tile_beg; tile < tile_end; ++tile) {
-    const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, bt = tile / (tiles_x * tiles_y), t = bt % T;
-    const int x0 = tx * 16, y0 = ty * 16;
-    __syncthreads();
-    // dy formation: all of a thread's 16 loads (4 positions x {y, argmax, dout, out}) are issued before the first is used, ahead of the halo's loads --
-    // with the conditional, dependent loads of the f32 kernel's loop a tile took 12 us of chained memory round trips.
-    // Coordinates are clamped instead of predicated (edge tiles: the values are discarded below).
-    float4 yv[4], dv[4], ov[4];
-    uchar4 am[4];
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int i = tid + it * 256, pos = i >> 2, cc = (i & 3) * 4;
-      const int oy = min(y0 + (pos >> 4), H - 1), ox = min(x0 + (pos & 15), W - 1);
-      const int py = min(c1_pdiv(oy, bn.pool), bn.Hp - 1), px = min(c1_pdiv(ox, bn.pool), bn.Wp - 1);
-      const int64_t pp = (((int64_t)bt * bn.Hp + py) * bn.Wp + px) * 16 + cc;
-      yv[it] = *reinterpret_cast<const float4*>(yconv + (((int64_t)bt * H + oy) * W + ox) * 16 + cc);
-      am[it] = *reinterpret_cast<const uchar4*>(bn.argmax + pp);
-      dv[it] = *reinterpret_cast<const float4*>(bn.dout + pp);
-      ov[it] = *reinterpret_cast<const float4*>(bn.out + pp);
-    }
-    for (int i = tid; i < 1200; i += 256) halo[i / 400][(i % 400) / 20][i % 20] = f2bf(c1_halo_f32(x, i, bt, t, y0, x0, T, H, W));
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int i = tid + it * 256, pos = i >> 2, cc = (i & 3) * 4;
-      const int oy = y0 + (pos >> 4), ox = x0 + (pos & 15);
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (oy < H && ox < W) {
-        const int py = c1_pdiv(oy, bn.pool), px = c1_pdiv(ox, bn.pool);
-        float gg[4] = {0.f, 0.f, 0.f, 0.f};
-        if (py < bn.Hp && px < bn.Wp) {
-          const int here = (oy - py * bn.pool) * bn.pool + (ox - px * bn.pool);
-          if (am[it].x == here) gg[0] = dv[it].x * leaky_slope(ov[it].x);
-          if (am[it].y == here) gg[1] = dv[it].y * leaky_slope(ov[it].y);
-          if (am[it].z == here) gg[2] = dv[it].z * leaky_slope(ov[it].z);
-          if (am[it].w == here) gg[3] = dv[it].w * leaky_slope(ov[it].w);
-        }
-        const float4 mu = *reinterpret_cast<const float4*>(bn.mean + cc), is = *reinterpret_cast<const float4*>(bn.invstd + cc);
-        const float4 k0 = *reinterpret_cast<const float4*>(bn.coef + cc), k1 = *reinterpret_cast<const float4*>(bn.coef + 16 + cc);
-        const float4 k2 = *reinterpret_cast<const float4*>(bn.coef + 32 + cc);
-        v.x = bn_dy(gg[0], yv[it].x, mu.x, is.x, k0.x, k1.x, k2.x);
-        v.y = bn_dy(gg[1], yv[it].y, mu.y, is.y, k0.y, k1.y, k2.y);
-        v.z = bn_dy(gg[2], yv[it].z, mu.z, is.z, k0.z, k1.z, k2.z);
-        v.w = bn_dy(gg[3], yv[it].w, mu.w, is.w, k0.w, k1.w, k2.w);
-      }
-      dyT[(cc + 0) * DYS + pos] = f2bf(v.x);
-      dyT[(cc + 1) * DYS + pos] = f2bf(v.y);
-      dyT[(cc + 2) * DYS + pos] = f2bf(v.z);
-      dyT[(cc + 3) * DYS + pos] = f2bf(v.w);
-    }
-    __syncthreads();
-    const char* hb0 = reinterpret_cast<const char*>(&halo[0][0][0]);
-#pragma unroll
-    for (int ksl = 0; ksl < 2; ++ksl) {
-      const int ks = wv * 2 + ksl;                                   // positions 32 ks .. 32 ks + 31 = tile rows 2 ks, 2 ks + 1
-      const bf16x8 fb = *reinterpret_cast<const bf16x8*>(dyT + l16 * DYS + 32 * ks + 8 * g);
-      const char* hb = hb0 + ks * (2 * 24 * 2);
-#pragma unroll
-      for (int mt = 0; mt < 5; ++mt) {
-        const unsigned short* ap = reinterpret_cast<const unsigned short*>(hb + abase[mt]);
-        const unsigned a0 = ap[0] | ((unsigned)ap[1] << 16), a1 = ap[2] | ((unsigned)ap[3] << 16);
-        const unsigned a2 = ap[4] | ((unsigned)ap[5] << 16), a3 = ap[6] | ((unsigned)ap[7] << 16);
-        Mma<MODE_BF16>::mma(acc[mt], __builtin_bit_cast(bf16x8, make_uint4(a0, a1, a2, a3)), fb);
-      }
-    }
-  }
-  // ---- sum the four waves: lane (co = l16, g) holds taps 16 mt + 4 g + r
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);                        // [4 waves][80 taps][16 co]
-#pragma unroll
-  for (int mt = 0; mt < 5; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[(wv * 80 + 16 * mt + 4 * g + r) * 16 + l16] = acc[mt][r];
-  __syncthreads();
-  for (int i = tid; i < 1200; i += 256) {     // i = c * 75 + tap: [chunk][c][tap]
-    const int c = i / 75, tap = i % 75;
-    partials[(int64_t)chunk * 1200 + i] = red[tap * 16 + c] + red[(80 + tap) * 16 + c] + red[(160 + tap) * 16 + c] + red[(240 + tap) * 16 + c];
-  }
-}
-
-// conv3d_c1_wgrad_recompute_kernel: the same product WITHOUT the stored conv output: the tile's y is recomputed from the halo that is
-// staged anyway (C1Conv on an IEEE-half image of it: the arithmetic of conv3d_c1_fwd_mfma_kernel, so xhat is bit-identical to what the
-// forward normalised).  The MFMA result layout -- lane (column l16, channel group g) holds channels 4 g .. 4 g + 3 of the positions
-// (row 4 wv + i, l16) -- is also the dy-formation mapping: each lane forms its 4 x 4 values from registers and writes them transposed.
-// The bf16 halo of the weight-gradient product is kept in the same four-shifted-copies form: the A fragment of lane (tap, k group) is 8
-// consecutive columns starting at kw + 8 (g & 1), i.e. copy kw & 3 at an 8-byte aligned column -- one ds_read2_b64 instead of eight
-// 16-bit reads and four packs.  Both images are double-buffered and the next tile's halo is fetched a tile ahead.
-__global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                        float* __restrict__ partials, int T, int H, int W, int tiles_x,
-                                                                        int tiles_y, int BT, int tiles_per_chunk, int nchunk, C1BnArgs bn) {
-  constexpr int DYS = 256 + 8;
-  // [2 buffers][half image | bf16 image] + dyT; the final reduction (20480 B) reuses the front
-  __shared__ __attribute__((aligned(16))) unsigned short img[2][2][C1H_IMG_ALLOC];
+  constexpr int NIMG = RECOMPUTE ? 2 : 1;                             // images per buffer: [IEEE half |] bf16
+  constexpr int RED = 4 * 80 * 16 * 4;                                // bytes of the final reduction [4 waves][80 taps][16 co] f32, which reuses the buffers
+  constexpr int IMG = RECOMPUTE ? C1H_IMG_ALLOC : RED / 4;            // halves per image: two bf16-only images (19232 B) are padded up to RED
+  static_assert(IMG >= C1H_IMG_ALLOC && IMG % 8 == 0, "halo image");
+  __shared__ __attribute__((aligned(16))) unsigned short img[2][NIMG][IMG];
   __shared__ __attribute__((aligned(16))) unsigned short dyT[16 * DYS];
-  static_assert(sizeof(unsigned short) * 4 * C1H_IMG_ALLOC >= 4 * 80 * 16 * 4, "reduction scratch");
+  static_assert(sizeof(img) >= RED, "reduction scratch");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l16 = lane & 15, g = lane >> 4;
   const int tiles_total = BT * tiles_x * tiles_y;
   const int chunk = xcd_chunk(nchunk);
   if (chunk >= nchunk) return;
-  for (int i = tid; i < 4 * C1H_IMG_ALLOC / 8; i += 256) reinterpret_cast<uint4*>(&img[0][0][0])[i] = make_uint4(0, 0, 0, 0);
+  // columns 20 - s .. 19 of copy s are never written: zero once
+  for (int i = tid; i < 2 * NIMG * IMG / 8; i += 256) reinterpret_cast<uint4*>(&img[0][0][0])[i] = make_uint4(0, 0, 0, 0);
   // byte offsets of the A fragments of the 5 tap tiles (K step ks: add 80 ks)
   unsigned abase[5];
 #pragma unroll
@@ -575,15 +478,16 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
     abase[mt] = (unsigned)(((kw & 3) * C1H_COPY + (kd * 20 + kh + (g >> 1)) * 20 + (kw & ~3) + 8 * (g & 1)) * 2);
   }
   C1Conv cv;
-  cv.setup(w, l16, g, wv);
+  if constexpr (RECOMPUTE) cv.setup(src, l16, g, wv);
   C1Halo hl;
   hl.setup(tid, H, W);
   // the per-channel constants of the dy formula live in LDS (24 registers otherwise, which cost the third wave per SIMD)
-  __shared__ __attribute__((aligned(16))) float cst[6][16];          // mean, invstd, gamma invstd, mean(dz), mean(dz xhat), beta - mean gamma invstd
+  // mean, invstd, gamma invstd, mean(dz), mean(dz xhat) and, to recompute the sign, beta - mean gamma invstd
+  __shared__ __attribute__((aligned(16))) float cst[RECOMPUTE ? 6 : 5][16];
   if (tid < 16) {
     const float m_ = bn.mean[tid], c0_ = bn.coef[tid];
     cst[0][tid] = m_; cst[1][tid] = bn.invstd[tid]; cst[2][tid] = c0_; cst[3][tid] = bn.coef[16 + tid]; cst[4][tid] = bn.coef[32 + tid];
-    cst[5][tid] = bn_shift(bn.beta[tid], m_, c0_);
+    if constexpr (RECOMPUTE) cst[5][tid] = bn_shift(bn.beta[tid], m_, c0_);
   }
   f32x4 acc[5];
 #pragma unroll
@@ -599,8 +503,8 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
     unsigned short h16[5], b16[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) { h16[j] = Mma<MODE_F16>::cvt(hreg[j]); b16[j] = f2bf(hreg[j]); }
-    hl.stash(&img[buf][0][0], tid, h16);
-    hl.stash(&img[buf][1][0], tid, b16);
+    if constexpr (RECOMPUTE) hl.stash(&img[buf][0][0], tid, h16);
+    hl.stash(&img[buf][NIMG - 1][0], tid, b16);
   };
   hl.fetch(x, tid, bt, t, ty * 16, tx * 16, T, H, W, hreg);
   __syncthreads();                                                   // zero fill complete
@@ -609,27 +513,34 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
   for (int tile = tile_beg, it = 0; tile < tile_end; ++tile, ++it) {
     const int x0 = tx * 16, y0 = ty * 16, cbt = bt;
     if (++tx == tiles_x) { tx = 0; if (++ty == tiles_y) { ty = 0; ++bt; if (++t == T) t = 0; } }
-    // the pooled operands of this lane's four positions and the next tile's halo: issued first, used after the conv
-    float4 dv[4];
+    // the operands of this lane's four positions and the next tile's halo: issued first, used after the conv.  Coordinates are
+    // clamped instead of predicated (edge tiles: the values are discarded below).
+    float4 dv[4], ov[4];
     uchar4 am[4];
+    f32x4 z[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int oy = min(y0 + 4 * wv + i, H - 1), ox = min(x0 + l16, W - 1);
       const int py = min(c1_pdiv(oy, bn.pool), bn.Hp - 1), px = min(c1_pdiv(ox, bn.pool), bn.Wp - 1);
       const int64_t pp = (((int64_t)cbt * bn.Hp + py) * bn.Wp + px) * 16 + 4 * g;
+      if constexpr (!RECOMPUTE) z[i] = *reinterpret_cast<const f32x4*>(src + (((int64_t)cbt * H + oy) * W + ox) * 16 + 4 * g);
       am[i] = *reinterpret_cast<const uchar4*>(bn.argmax + pp);
       dv[i] = *reinterpret_cast<const float4*>(bn.dout + pp);
+      if constexpr (!RECOMPUTE) ov[i] = *reinterpret_cast<const float4*>(bn.out + pp);
     }
     if (tile + 1 < tile_end) hl.fetch(x, tid, bt, t, ty * 16, tx * 16, T, H, W, hreg);
     // ---- y of the tile (forward arithmetic)
-    f32x4 z[4];
+    if constexpr (RECOMPUTE) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    cv.tile(&img[it & 1][0][0], z);
+      for (int i = 0; i < 4; ++i) z[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      cv.tile(&img[it & 1][0][0], z);
+    }
     // ---- dy of this lane's positions, transposed bf16 into LDS
     const float4 mu = *reinterpret_cast<const float4*>(&cst[0][4 * g]), is = *reinterpret_cast<const float4*>(&cst[1][4 * g]);
     const float4 k0 = *reinterpret_cast<const float4*>(&cst[2][4 * g]), k1 = *reinterpret_cast<const float4*>(&cst[3][4 * g]);
-    const float4 k2 = *reinterpret_cast<const float4*>(&cst[4][4 * g]), sh = *reinterpret_cast<const float4*>(&cst[5][4 * g]);
+    const float4 k2 = *reinterpret_cast<const float4*>(&cst[4][4 * g]);
+    float4 sh = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (RECOMPUTE) sh = *reinterpret_cast<const float4*>(&cst[5][4 * g]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int oy = y0 + 4 * wv + i, ox = x0 + l16, pos = (4 * wv + i) * 16 + l16;
@@ -639,12 +550,12 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
         float gg[4] = {0.f, 0.f, 0.f, 0.f};
         if (py < bn.Hp && px < bn.Wp) {
           const int here = (oy - py * bn.pool) * bn.pool + (ox - px * bn.pool);
-          // the pooled output is positive exactly when the forward's pre-activation at the argmax was: bn_affine with (gamma invstd,
-          // beta - mean gamma invstd), as conv3d_c1_fwd_mfma_kernel<2> formed it on the same recomputed y -- `out` is not read
-          if (am[i].x == here) gg[0] = dv[i].x * leaky_slope(bn_affine(z[i][0], k0.x, sh.x));
-          if (am[i].y == here) gg[1] = dv[i].y * leaky_slope(bn_affine(z[i][1], k0.y, sh.y));
-          if (am[i].z == here) gg[2] = dv[i].z * leaky_slope(bn_affine(z[i][2], k0.z, sh.z));
-          if (am[i].w == here) gg[3] = dv[i].w * leaky_slope(bn_affine(z[i][3], k0.w, sh.w));
+          // RECOMPUTE: the pooled output is positive exactly when the forward's pre-activation at the argmax was: bn_affine with
+          // (gamma invstd, beta - mean gamma invstd), as conv3d_c1_fwd_mfma_kernel<2> formed it on the same recomputed y -- `out` is not read
+          if (am[i].x == here) gg[0] = dv[i].x * leaky_slope(RECOMPUTE ? bn_affine(z[i][0], k0.x, sh.x) : ov[i].x);
+          if (am[i].y == here) gg[1] = dv[i].y * leaky_slope(RECOMPUTE ? bn_affine(z[i][1], k0.y, sh.y) : ov[i].y);
+          if (am[i].z == here) gg[2] = dv[i].z * leaky_slope(RECOMPUTE ? bn_affine(z[i][2], k0.z, sh.z) : ov[i].z);
+          if (am[i].w == here) gg[3] = dv[i].w * leaky_slope(RECOMPUTE ? bn_affine(z[i][3], k0.w, sh.w) : ov[i].w);
         }
         v.x = bn_dy(gg[0], z[i][0], mu.x, is.x, k0.x, k1.x, k2.x);
         v.y = bn_dy(gg[1], z[i][1], mu.y, is.y, k0.y, k1.y, k2.y);
@@ -657,7 +568,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
       dyT[(4 * g + 3) * DYS + pos] = f2bf(v.w);
     }
     __syncthreads();
-    const char* hb0 = reinterpret_cast<const char*>(&img[it & 1][1][0]);
+    const char* hb0 = reinterpret_cast<const char*>(&img[it & 1][NIMG - 1][0]);
 #pragma unroll
     for (int ksl = 0; ksl < 2; ++ksl) {
       const int ks = wv * 2 + ksl;                                   // positions 32 ks .. 32 ks + 31 = tile rows 2 ks, 2 ks + 1
@@ -673,7 +584,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_recompute_kernel(const fl
     __syncthreads();
   }
   // ---- sum the four waves: lane (co = l16, g) holds taps 16 mt + 4 g + r
-  float* red = reinterpret_cast<float*>(&img[0][0][0]);              // [4 waves][80 taps][16 co]
+  float* red = reinterpret_cast<float*>(&img[0][0][0]);                      // [4 waves][80 taps][16 co]
 #pragma unroll
   for (int mt = 0; mt < 5; ++mt)
 #pragma unroll
@@ -744,18 +655,18 @@ extern "C" int maavss_conv3d_c1_bn_pool_act(const float* x, const float* w, cons
   return MAAVSS_OK;
 }
 
-// one of the three weight-gradient kernels (C1_VALU without `bn`: the plain gradient from dy) and the reduction of its partials;
+// one of the weight-gradient kernels (C1_VALU without `bn`: the plain gradient from dy) and the reduction of its partials;
 // `src` is dy, the stored conv output y, or for C1_RECOMPUTE the layer's weights
 enum C1Wgrad { C1_VALU, C1_MFMA, C1_RECOMPUTE };
 static int c1_wgrad_launch(C1Wgrad which, const float* x, const float* src, float* dw, float* ws, int nchunk, int B, int T, int H, int W, int beta,
                            const C1BnArgs* bn, hipStream_t st) {
   const int tiles_x = cdiv(W, 16), tiles_y = cdiv(H, 16);
   C1BnArgs none = {};
-  auto kern = which == C1_RECOMPUTE ? conv3d_c1_wgrad_recompute_kernel : which == C1_MFMA ? conv3d_c1_wgrad_mfma_kernel
+  auto kern = which == C1_RECOMPUTE ? conv3d_c1_wgrad_mfma_kernel<true> : which == C1_MFMA ? conv3d_c1_wgrad_mfma_kernel<false>
               : bn              ? conv3d_c1_wgrad_kernel<true> : conv3d_c1_wgrad_kernel<false>;
   hipLaunchKernelGGL(kern, dim3(cdiv(nchunk, 8) * 8), dim3(256), 0, st, x, src, ws, T, H, W, tiles_x, tiles_y, B * T,
                      cdiv(c1_tiles(B, T, H, W), nchunk), nchunk, bn ? *bn : none);
-  MAAVSS_LAUNCH_CHECK(which == C1_RECOMPUTE ? "conv3d_c1_wgrad_recompute_kernel" : "conv3d_c1_wgrad_kernel");
+  MAAVSS_LAUNCH_CHECK(which == C1_VALU ? "conv3d_c1_wgrad_kernel" : "conv3d_c1_wgrad_mfma_kernel");
   conv3d_c1_wgrad_reduce(ws, dw, nchunk, beta, st);
   MAAVSS_LAUNCH_CHECK("conv3d_c1_wgrad_reduce_kernel");
   return MAAVSS_OK;
@@ -770,7 +681,7 @@ extern "C" int maavss_conv3d_c1_wgrad(const float* x, const float* dy, float* dw
 }
 
 // maavss_conv3d_c1_wgrad_bn on the 16-bit path without the stored conv output: `w` = the layer's weights [16][1][3][5][5], y is
-// recomputed per tile (conv3d_c1_wgrad_recompute_kernel).  bf16 backward operands, IEEE-half forward operands for the recompute.
+// recomputed per tile (conv3d_c1_wgrad_mfma_kernel<true>).  bf16 backward operands, IEEE-half forward operands for the recompute.
 extern "C" int maavss_conv3d_c1_wgrad_bn_recompute(const float* x, const float* w, const float* dout, const void* argmax,
                                                    const float* mean, const float* invstd, const float* bn_beta, const float* coef, int pool,
                                                    float* dw, float* ws, int nchunk, int B, int T, int H, int W, int beta, void* stream) {

@@ -144,7 +144,7 @@ class _Conv3dEmu(nn.Conv3d):
 
 class _Conv3d16bitL0(torch.autograd.Function):
     """layer 0 (C_in = 1) of the HIP 16-bit path: IEEE-half operands on the MFMA in the forward pass; weight gradient with x and
-    dy rounded to bf16 (conv3d_c1_wgrad_mfma_kernel); the network input needs no gradient"""
+    dy rounded to bf16 (conv3d_c1_wgrad_mfma_kernel<false|true>); the network input needs no gradient"""
 
     @staticmethod
     def forward(ctx, x, w, pad):

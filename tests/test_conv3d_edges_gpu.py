@@ -294,6 +294,27 @@ def test_c1_fused_bn_weight_gradient(b, t, h, w, pool):
     report(tag + f" (f16 conv output, undecided {share:.4f})", **fr)
 
 
+@pytest.mark.parametrize("b,t,h,w,pool", cs.C1_BN_CASES)
+def test_c1_fused_bn_weight_gradient_from_the_stored_and_the_recomputed_output_is_bit_identical(b, t, h, w, pool):
+    """The two instantiations of conv3d_c1_wgrad_mfma_kernel -- y read from memory, y recomputed per tile -- form the same product
+    in the same order: on the IEEE-half MFMA forward's y (what the recompute reproduces; the sign of `out` and of the recomputed
+    pre-activation agree through bn_act.h) they return the same bits.  Partial tiles in both directions, a pool window cut off at
+    the border, pool 3, and an empty chunk (tiles + 1 chunks) on poisoned workspaces."""
+    from maavss_amd import ops
+    tiles = cref.c1_tiles(b, t, h, w)
+    f = _fused_inputs(ops, b, t, h, w, pool, F16)
+    args = (f["x"], f["y"], f["dout"], f["out"], f["arg"], f["mean"], f["invstd"], f["coef"], pool)
+    rargs = (f["x"], f["w"], f["dout"], f["arg"], f["mean"], f["invstd"], f["beta"], f["coef"], pool)
+    for nchunk in (None, 1, tiles + 1):
+        poison(1200 * (nchunk or max(1, min(1024, tiles // 2))))
+        stored = ops.conv3d_c1_wgrad_bn(*args, nchunk=nchunk, precise=BF16)
+        poison(1200 * (nchunk or max(1, min(1024, tiles // 2))))
+        recomputed = ops.conv3d_c1_wgrad_bn_recompute(*rargs, nchunk=nchunk)
+        assert bool(torch.isfinite(stored).all()), f"c1 fused bn {b}x{t}x{h}x{w} pool {pool} nchunk {nchunk}: not finite"
+        assert torch.equal(stored, recomputed), (f"c1 fused bn {b}x{t}x{h}x{w} pool {pool} nchunk {nchunk}: "
+                                                 f"{int((stored != recomputed).sum())} of 1200 elements differ")
+
+
 def test_c1_fused_bn_rejects_other_pools():
     """the entry points admit pool 2 and 3 only (c1_pdiv divides by nothing else)"""
     from maavss_amd import ops
