@@ -376,6 +376,35 @@ int maavss_sqerr_rows(const float* pred, const float* tgt, int64_t B, int64_t n,
 int maavss_metric_add_sum(const double* vals, int64_t n, int64_t stride, double weight, double* acc, void* stream);
 int maavss_metric_add_classes(const double* vals, const double* minus, int64_t n, int64_t stride, int cols, double* acc, void* stream);
 
+/* ---- EXTENSION: intelligibility scores (maavss_amd.stoi_metrics, Validator(intelligibility_sr=...)) -----------------------------
+ * maavss_stoi: short-time objective intelligibility (STOI, Taal et al. 2011) and its extended form (ESTOI, Jensen & Taal 2016) of est
+ * [rows][n] against ref [rows][n], f32 sampled at 10 kHz, per row.  Samples are widened to f64 on load and every operation from there on is
+ * f64 in a fixed order: no floating-point atomics, two runs give identical bytes.  Added without a version bump.  Row strides in elements,
+ * >= 0, rows may overlap, ignored when rows = 1; the pointers need 4-byte alignment only.  tests/stoi_twin.py is the float64 restatement.
+ *   window    w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i < 256
+ *   frames    a signal of L samples has nf(L) = len(range(0, L - 256, 128)) frames, frame k = samples [128 k, 128 k + 256): one frame fewer
+ *             than fit when L - 256 is a multiple of 128 (the convention of the widely used Python implementation, kept)
+ *   silence   E[k] = sum_i (w[i] ref[128 k + i])^2; frame k is kept iff E[k] 1e4 > max E (40 dB under the loudest frame).  The silence-free
+ *             ref and est are the overlap-add at hop 128 of their kept windowed frames (one mask, the reference's): n_kept frames
+ *   bands     the silence-free signals are framed again (M = n_kept - 1 frames), windowed again, zero-padded to 512 and transformed;
+ *             X[j][k] (ref) and Y[j][k] (est) = sqrt of the summed powers of bins [lo[j], hi[j]), 15 third-octave bands from 150 Hz:
+ *             lo = 7 9 11 14 17 22 27 34 43 55 69 87 109 138 174, hi = lo[1:], 219
+ *   segments  columns [m - 30, m) for m = 30 .. M: M - 29 segments (384 ms each)
+ *   STOI      per band of a segment: y' = min(alpha y, x (1 + 10^(15/20))), alpha = |x| / (|y| + eps); x and y' minus their means, each
+ *             divided by (its norm + eps), dot product.  The score is the mean over the 15 bands and all segments.  eps = 2^-52
+ *   ESTOI     per segment, x and y alike: each band minus its mean over time, divided by (its norm + eps); then each frame minus its mean
+ *             over bands, divided by (its norm + eps); sum(xn yn) / 30.  The score is the mean over segments
+ * Two deviations from that Python implementation: (1) the mask compares squared norms directly, without its eps inside a logarithm; (2) a
+ * row without a segment (M < 30: too short, too much silence, an all-silent reference, max E = 0) scores NaN with n_segments = 0 where the
+ * package returns 1e-5 and warns.  A non-finite sample anywhere in est or ref gives NaN, NaN, 0, 0 for that row only (an explicit flag).
+ * out [rows][4] f64: stoi, estoi, n_kept, n_segments.  n < 2^31.  ws: maavss_stoi_ws_bytes(rows, n) bytes (0 for invalid arguments), 8-byte
+ * aligned: the window and twiddle tables, per (row, frame) E, the flag and src[], per row the counts, X and Y [rows][2][15][nf - 1] and
+ * per (row, segment) the two partial scores.  Launches: tables, energies, select, [bands, segments when nf(n) > 30], finalize; the
+ * silence-free waveform is never written. */
+int64_t maavss_stoi_ws_bytes(int64_t rows, int64_t n);
+int maavss_stoi(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t rows, int64_t n, double* out, void* ws,
+                int64_t ws_bytes, void* stream);
+
 /* K18 helper, EXTENSION (the reference is single-device): bf16 wire format of the data-parallel gradient all-reduce -- a bucket of
  * the flat f32 gradient buffer is rounded to bf16 (round-to-nearest-even) for the collective and widened back into the f32 master
  * buffer afterwards (trainer.GradSync(wire_dtype="bf16")).  n a multiple of 8, buffers 16-byte aligned. */

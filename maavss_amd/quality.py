@@ -8,7 +8,8 @@ example is judged by (csrc/quality_metrics.hip: f64 sums of the f32 data in a fi
 * `plan_wave_chunks` -- the host-side chunk planner of the wave metrics (pure, no device)
 * `wave_metrics`     -- per row of est [B, L] against ref [B, L]: Sxx, Syy, Sxy, See, Srr, SNR, SI-SDR, segmental SNR
 * `spectrum_metrics` -- per row of pred [B, 2, T, F] against tgt: squared-error sum and log-spectral distance
-* `Validator`        -- an additive device accumulator of both over batches, clips and recordings; `result()` makes the one copy
+* `Validator`        -- an additive device accumulator of both over batches, clips and recordings; `result()` makes the one copy;
+                        with `intelligibility_sr=` also of STOI and ESTOI per clip (maavss_amd/stoi.py, csrc/stoi.hip)
 
 Definitions (include/maavss.h states them next to the entry points; tests/quality_twin.py is their float64 restatement):
   snr_db = 10 log10(Sxx / See), si_sdr_db = 10 log10(alpha^2 Sxx / Srr) with alpha = Sxy / Sxx and Srr = sum (est - alpha ref)^2 summed
@@ -19,6 +20,7 @@ Nothing here synchronises with the host before `Validator.result()`.
 import torch
 
 from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr, workspace
+from .stoi import stoi_metrics
 from .trainer import sliding_windows
 
 WAVE_COLUMNS = ("sxx", "syy", "sxy", "see", "srr", "snr_db", "si_sdr_db", "seg_snr_db", "n_frames")
@@ -117,6 +119,9 @@ def sqerr_rows(pred, tgt):
 _SUMS = ("stft", "lsd", "attn")
 _GROUPS = ("est", "noisy", "gain")
 _ACC_LEN = 2 * len(_SUMS) + 5 * len(WAVE_DB) * len(_GROUPS)
+# the second accumulator, only with intelligibility_sr: the same five numbers for stoi and estoi of the same three groups
+_INTEL = ("stoi", "estoi")
+_INTEL_LEN = 5 * len(_INTEL) * len(_GROUPS)
 
 
 class Validator:
@@ -136,7 +141,13 @@ class Validator:
     The accumulator is one small f64 device tensor (`.acc`) of sums and counts only, so it is additive: the element-wise sum of the
     accumulators of several ranks is the accumulator of their data.  `add_*` enqueue kernels on the current stream and never wait."""
 
-    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10):
+    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10, intelligibility_sr=None):
+        """intelligibility_sr: the sample rate of the waves given to add_waves / add_recording; with it they also add STOI and ESTOI
+        (maavss_amd.stoi_metrics) of the estimate, of the noisy input and of estimate minus noisy per clip, into a second small
+        accumulator (`.acc_intel`), and result() gains their keys.  None (the default): nothing of that is launched or reported."""
+        if intelligibility_sr is not None and (isinstance(intelligibility_sr, bool) or not isinstance(intelligibility_sr, int)
+                                               or intelligibility_sr < 1):
+            raise ValueError(f"intelligibility_sr must be None or a positive integer (samples per second), got {intelligibility_sr!r}")
         if int(num_seq) < 1:
             raise ValueError("num_seq must be >= 1")
         if int(seg_len) < 1:
@@ -145,17 +156,24 @@ class Validator:
             raise ValueError("lsd_floor must be > 0 (a power)")
         self.model, self.loss_coeff, self.num_seq = model, float(loss_coeff), int(num_seq)
         self.seg_len, self.lsd_floor = int(seg_len), float(lsd_floor)
+        self.intelligibility_sr = intelligibility_sr
         self.acc = None
+        self.acc_intel = None        # with intelligibility_sr: the tail of the allocation `acc` heads, so that result() makes one copy
+        self._buf = None
         self.best = None
 
     def reset(self):
         """Clear the accumulator (the best val_loss `improved` keeps is not touched)."""
-        if self.acc is not None:
-            self.acc.zero_()
+        if self._buf is not None:
+            self._buf.zero_()
 
     def _acc(self, dev):
         if self.acc is None:
-            self.acc = torch.zeros(_ACC_LEN, dtype=torch.float64, device=dev)
+            extra = 0 if self.intelligibility_sr is None else _INTEL_LEN
+            self._buf = torch.zeros(_ACC_LEN + extra, dtype=torch.float64, device=dev)
+            self.acc = self._buf[:_ACC_LEN]
+            if extra:
+                self.acc_intel = self._buf[_ACC_LEN:]
         return self.acc
 
     def _slot(self, kind, group=None):
@@ -208,6 +226,15 @@ class Validator:
                 raise ValueError("noisy must have the shape of est")
             call("maavss_metric_add_classes", ptr(mn[:, _DB0:]), None, b, cols, k, ptr(self._slot(None, "noisy")), st)
             call("maavss_metric_add_classes", ptr(m[:, _DB0:]), ptr(mn[:, _DB0:]), b, cols, k, ptr(self._slot(None, "gain")), st)
+        if self.intelligibility_sr is not None:
+            s = stoi_metrics(est, ref, self.intelligibility_sr)["raw"]
+            cols, k = s.shape[1], len(_INTEL)
+            slot = {g: self.acc_intel[5 * k * i:5 * k * (i + 1)] for i, g in enumerate(_GROUPS)}
+            call("maavss_metric_add_classes", ptr(s), None, b, cols, k, ptr(slot["est"]), st)
+            if noisy is not None:
+                sn = stoi_metrics(noisy, ref, self.intelligibility_sr)["raw"]
+                call("maavss_metric_add_classes", ptr(sn), None, b, cols, k, ptr(slot["noisy"]), st)
+                call("maavss_metric_add_classes", ptr(s), ptr(sn), b, cols, k, ptr(slot["gain"]), st)
 
     def add_recording(self, enhancer, noisy, clean, frames=None, attn=None):
         """Enhance `noisy` [L] with `enhancer(noisy, frames= | attn=)` -> (wave, start) and measure the estimate and the noisy input against
@@ -229,12 +256,14 @@ class Validator:
         val_loss_stft, val_loss_attn (total squared error over total elements: a ragged last batch is weighted by its size), val_loss =
         stft + loss_coeff * attn, lsd_db (mean over windows), n_windows; per wave metric m in snr_db, si_sdr_db, seg_snr_db: m (the mean
         over the clips whose value is finite) and m_n_finite / _n_posinf / _n_neginf / _n_nan; with noisy inputs also noisy_m (and its
-        counts) and m_improvement = the mean over clips of estimate minus noisy; n_clips.  A quantity nothing was added to is NaN."""
+        counts) and m_improvement = the mean over clips of estimate minus noisy; n_clips.  A quantity nothing was added to is NaN.
+        With intelligibility_sr also stoi, estoi, noisy_stoi, noisy_estoi, stoi_improvement, estoi_improvement (always all six) and
+        their _n_finite / _n_nan counts: a clip without a 384 ms segment, or with a non-finite sample, counts as NaN."""
         nan = float("nan")
-        if self.acc is None:
-            h = [0.0] * _ACC_LEN
+        if self._buf is None:
+            h = [0.0] * (_ACC_LEN + (0 if self.intelligibility_sr is None else _INTEL_LEN))
         else:
-            h = self.acc.cpu().tolist()
+            h = self._buf.cpu().tolist()
 
         def ratio(s, n):
             return s / n if n > 0 else nan
@@ -254,6 +283,14 @@ class Validator:
                 key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
                 out[key] = ratio(s, nf)
                 out.update({f"{key}_n_finite": int(nf), f"{key}_n_posinf": int(npos), f"{key}_n_neginf": int(nneg), f"{key}_n_nan": int(nnan)})
+        if self.intelligibility_sr is not None:
+            for group in _GROUPS:
+                for name in _INTEL:
+                    s, nf, _, _, nnan = h[o:o + 5]          # a score is a correlation: never infinite
+                    o += 5
+                    key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
+                    out[key] = ratio(s, nf)
+                    out.update({f"{key}_n_finite": int(nf), f"{key}_n_nan": int(nnan)})
         return out
 
     def improved(self, result):
