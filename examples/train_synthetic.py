@@ -12,6 +12,8 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --mix 2 --mix_snr 0 10                 # mix-and-separate: every clip + 2 others of the batch at 0..10 dB
     python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
     python examples/train_synthetic.py --val 2                                # every 2 steps: held-out loss and LSD, a checkpoint on improvement
+    python examples/train_synthetic.py --bank 8 [--bank_storage u16]          # the ViT once per recording: maps and audio of 8 recordings in
+                                                                              # HBM (ClipBank), every batch cut from them by clip index
 """
 import argparse
 import os
@@ -53,7 +55,13 @@ def main():
     ap.add_argument("--val", type=int, default=0, metavar="N",
                     help="every N steps, validate on one fixed seeded held-out batch (maavss_amd.Validator: train_av_net.py:147-181) and "
                          "save a checkpoint when the validation loss improves")
+    ap.add_argument("--bank", type=int, default=0, metavar="R",
+                    help="bank R synthetic recordings of 4 clips once (ViT + audio, maavss_amd.ClipBank: the reference's attn_frames_path / "
+                         "use_audio_memmap), then draw every batch by clip index from a seeded permutation: no ViT in the step")
+    ap.add_argument("--bank_storage", choices=("f32", "u16"), default="f32", help="with --bank: 4 or 2 bytes per map value")
     a = ap.parse_args()
+    if a.bank and (a.raw_video or a.raw_audio or a.overfit):
+        ap.error("--bank holds transformed frames' maps and 16 kHz audio: it does not go with --raw_video, --raw_audio or --overfit")
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
     t_total = nf + ns - 1                                      # frames per clip so that num_seq windows fit (av_dataset.py:251-278)
@@ -74,12 +82,14 @@ def main():
         audio_transform = maavss_amd.AudioTransform(16000, compress_audio=a.compress_audio)
         raw_length = audio_transform.input_length(length, raw_sr)      # the fewest 44.1 kHz samples that give `length` at 16 kHz
     mixer = maavss_amd.Mixer(stft, a.mix, tuple(a.mix_snr)) if a.mix else None
-    pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform, audio_transform=audio_transform,
-                                   audio_length=length if a.raw_audio else None, mixer=mixer)
+    if not a.bank:
+        pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform, audio_transform=audio_transform,
+                                       audio_length=length if a.raw_audio else None, mixer=mixer)
 
     g = torch.Generator().manual_seed(0)
 
-    def batch():
+    def batch(b=b, t_total=t_total, length=length):
+        """b clips of t_total frames and `length` samples (--bank: one recording = one long clip)."""
         if transform is not None:
             frames = torch.randint(0, 256, (b, t_total, h0, w0, 3), generator=g, dtype=torch.uint8)
         else:
@@ -103,19 +113,51 @@ def main():
 
     fixed = batch() if a.overfit else None
     sr_arg = dict(audio_sr=raw_sr) if a.raw_audio else {}
+
+    if not a.bank:
+        def submit(seed):
+            pipe.submit(*(fixed or batch()), seed=seed, **sr_arg)
+    else:
+        # the reference's cached attention frames and audio memmap (train_avse_frames.py:50, av_dataset.py:136-147), on the device: every
+        # recording goes through the ViT once, here; clip k of a recording starts frame_hop frames after clip k - 1
+        per_rec, frame_hop = 4, max(1, t_total // 2)
+        n_f = (per_rec - 1) * frame_hop + t_total
+        n_s = (per_rec - 1) * frame_hop * 16000 // 30 + 1 + length
+        n_rec = a.bank + (-(-b // per_rec) if a.val else 0)          # --val: the last recordings are held out
+        bank = maavss_amd.ClipBank(w, t_total, frame_hop, hpf, hop, capacity_frames=n_rec * n_f, capacity_samples=n_rec * n_s,
+                                   storage=a.bank_storage, device=dev)
+        for _ in range(n_rec):
+            frames, audio = batch(1, n_f, n_s)
+            bank.add_recording(audio[0], frames=frames, video_attention=extractor)
+        n_train = a.bank * per_rec
+        if n_train < b:
+            ap.error(f"--bank {a.bank} holds {n_train} clips, fewer than one batch of {b}")
+        print(f"bank: {len(bank)} clips of {n_rec} recordings, {bank.maps.numel() * bank.maps.element_size() / 1e6:.2f} MB of maps "
+              f"({a.bank_storage}), {bank.audio.numel() * 4 / 1e6:.2f} MB of audio", flush=True)
+        pipe = maavss_amd.ClipPipeline(None, stft, clip_frames=t_total, bank=bank, mixer=mixer)
+        g_order, order = torch.Generator().manual_seed(0), []
+
+        def submit(seed):
+            while len(order) < b:                                        # the next epoch's permutation of the training clips
+                order.extend(torch.randperm(n_train, generator=g_order).tolist())
+            pipe.submit_clips([order.pop(0) for _ in range(b)], seed=seed)
+
     held_out = validator = val_dir = None
     if a.val:
         # one held-out batch from a generator of its own (the training stream's draws stay what they are without --val), extracted once
-        g_train, g = g, torch.Generator().manual_seed(12345)
-        pipe.submit(*batch(), seed=12345, **sr_arg)
+        if a.bank:
+            pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345)
+        else:
+            g_train, g = g, torch.Generator().manual_seed(12345)
+            pipe.submit(*batch(), seed=12345, **sr_arg)
+            g = g_train
         held_out = tuple(t.clone() for t in pipe.get())
         pipe.release()
-        g = g_train
         validator = maavss_amd.Validator(model, loss_coeff=0.001, num_seq=ns)
         val_dir = tempfile.TemporaryDirectory()
-    pipe.submit(*(fixed or batch()), seed=0, **sr_arg)
+    submit(0)
     for i in range(a.steps):
-        pipe.submit(*(fixed or batch()), seed=0 if a.overfit else i + 1, **sr_arg)      # extraction of the next batch: side stream
+        submit(0 if a.overfit else i + 1)                                # extraction of the next batch: side stream
         attn, x_stft, y_stft = pipe.get()                        # [B,1,T,H,W], [B,2,T_a,F] x 2
         losses = step.sliding_window_step(x_stft, y_stft, attn, attn, nf, hpf)
         pipe.release()

@@ -595,6 +595,31 @@ int maavss_av_stft_windows(const float* y, int64_t n_clips, int clip_rows, int n
 int maavss_av_stitch(const float* pred, const float* clip_absmax, int64_t n_clips, int num_seq, int hops_per_frame, int n_bins,
                      int64_t w0, int64_t n_win, float* out, void* stream);
 
+/* ---- EXTENSION: device-resident clip bank (maavss_amd.ClipBank) -----------------------------------------------------------------
+ * The reference trains from cached attention frames and one audio memmap of the whole dataset (av_dataset.py:251-268, 285-294:
+ * attn_frames_path, use_audio_memmap).  Here both stay in HBM: per-frame maps at patch resolution, [n_frames_total][(H/8) * (W/8)]
+ * as maavss_vit_attn_maps_pass1 writes them (each frame divided by its own maximum), stored as f32 (storage 0) or as 16-bit
+ * integers (storage 1), and every recording's samples in one f32 buffer.  A batch is cut from them by device tables of start
+ * positions.  The library does not allocate and does not synchronise; no atomics; additive symbols (nothing existing changed meaning).
+ * Pack: q = rint(min(max(v, 0), 1) * 65535), the product one f32 product, rounded half to even; NaN packs to 0.  Unpack: the
+ * correctly rounded f32 quotient q / 65535 (65535 gives exactly 1).  |unpack(pack(v)) - v| <= 1 / 131070 (half a step) + 2^-23 (the f32 roundings of the product and of the quotient) for v in [0, 1]. */
+int maavss_bank_pack_u16(const float* maps, void* out, int64_t n, void* stream);
+int maavss_bank_unpack_u16(const void* q, float* out, int64_t n, void* stream);
+/* out [n_clips][clip_frames][H][W] (16-byte aligned): frame t of clip b = bank frame clip_start[b] + t (device int32 [n_clips], clamped
+ * into [0, n_frames_total - clip_frames]), nearest x8 with zeros outside the patch grid, times clip_rcp[b] = 1 / (clip max) of
+ * av_dataset.py:328 over the clip's (unpacked) map values; attn_diff = 1: the zero-padded temporal difference of av_dataset.py:323-326
+ * and its maximum, clip frame 0 being 0 * clip_rcp[b] -- the frame in front of a clip is never read.  The f32 operations of
+ * maavss_av_clip_scale + maavss_av_attn_windows (num_seq = 1, win_frames = clip_frames), so storage 0 gives attention_frames(clip,
+ * clip_frames, attn_diff) bit for bit and storage 1 the same expression on the unpacked maps.  clip_rcp: n_clips floats of workspace.
+ * Two launches; n_clips * clip_frames * ceil(H / 8) * (W / 4) must stay below 2^31.  16-byte stores throughout. */
+int maavss_bank_attn_clips(const void* maps, int storage, const int32_t* clip_start, int64_t n_clips, int64_t n_frames_total,
+                           int clip_frames, int H, int W, int attn_diff, float* clip_rcp, float* out, void* stream);
+/* Row gather from the audio bank [n_samples]: out[b * ld_out + i] = bank[clip_start[b] + i], i < L; clip_start device int64 [n_clips]
+ * (8-byte aligned), clamped into [0, n_samples - L]; 64-bit offsets.  16-byte stores when out is 16-byte aligned and ld_out % 4 == 0
+ * (the source rows start anywhere and are read as dwords), element stores otherwise.  out must not overlap the bank. */
+int maavss_bank_audio_clips(const float* bank, int64_t n_samples, const int64_t* clip_start, int64_t n_clips, int64_t L, float* out,
+                            int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,307 @@
+"""A dataset's attention maps and audio resident in HBM, indexed in clips as the reference's dataset is.
+
+The reference trains from cached attention frames (train_avse_frames.py:50, `attn_frames_path`; av_dataset.py:251-268) and cuts the
+audio out of one memmap of the whole dataset (av_dataset.py:136-147, 285-294, `use_audio_memmap`): the frozen ViT runs once per
+frame, not once per epoch.  `ClipBank` is that cache on the device.  Per frame it keeps the map at patch resolution, (S/8)^2 values
+as maavss_vit_attn_maps_pass1 writes them (the frame divided by its own maximum), as f32 or as 16-bit integers; per recording the
+samples at `sr`.  `batch(indices)` cuts a training batch from both without the ViT, the host or a synchronisation
+(maavss_bank_attn_clips, maavss_bank_audio_clips; csrc/clip_bank.hip).
+
+Clip index (utilities.extract_clips -> VideoClips, av_dataset.py:285-289): clip k of a recording takes its frames
+[k*frame_hop, k*frame_hop + clip_frames) and its samples [s_k, s_k + hops_per_frame*hop*clip_frames) with
+s_k = round(k*frame_hop*sr/fps) (Python's round on the exact fraction, as enhance.clip_tiling rounds).  A recording holds the longest
+prefix of clips for which both its frames and its samples suffice, and the bank keeps the frames and samples those clips use.
+Clips are numbered through the recordings in the order these were added.
+
+Contract.  storage="f32": attn[b] is bit-identical to video_attention.attention_frames(frames[v:v+T], clip_frames=T,
+attn_diff=attn_diff) of the clip's frames, audio[b] to the clip's samples.  storage="u16": a map value v is kept as
+q = rint(min(max(v, 0), 1) * 65535) (one f32 product, half to even) and read back as the correctly rounded f32 quotient q / 65535;
+the batch is the f32 contract applied to those values (clip maximum over them, or over their zero-padded difference, then
+value * (1 / m)).  Against f32 storage the maps differ by at most 1/131070 (half a step; plus 2^-23 for the f32 roundings of the product
+and the quotient) before the clip normalisation, in half the bytes.
+A clip never reads a map or a sample of a neighbouring recording, with attn_diff too (clip frame 0 is 0 * (1 / m)).
+tests/bank_twin.py restates the pack and the index on the host.
+"""
+from bisect import bisect_right
+from fractions import Fraction
+
+import torch
+
+from . import _lib
+from ._lib import call, ptr, stream_ptr
+
+FORMAT = "maavss_amd.ClipBank"
+FORMAT_VERSION = 1
+_STORAGE = {"f32": (0, torch.float32), "u16": (1, torch.int16)}      # the u16 payload lives in int16 tensors (bit patterns)
+
+
+def clip_sample_start(k, frame_hop, fps=30, sr=16000):
+    """s_k: the first sample of a recording's clip k."""
+    return round(k * frame_hop * Fraction(sr) / Fraction(fps))
+
+
+def count_clips(n_frames, n_samples, clip_frames, frame_hop, clip_samples, fps=30, sr=16000):
+    """The longest prefix of clips that n_frames frames and n_samples samples hold."""
+    k = 0
+    while k * frame_hop + clip_frames <= n_frames and clip_sample_start(k, frame_hop, fps, sr) + clip_samples <= n_samples:
+        k += 1
+    return k
+
+
+def _positive_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    return v
+
+
+class ClipBank:
+    """`bank = ClipBank(frame_size, clip_frames, frame_hop, hops_per_frame, hop, capacity_frames=.., capacity_samples=..)`;
+    `bank.add_recording(audio, frames=.., video_attention=va)` once per recording; `attn, audio = bank.batch(indices)` per step.
+
+    frame_size S: frames are S x S, S % 4 == 0, S >= 8, patch grid S // 8 squared.  The map buffer [capacity_frames][(S//8)^2] and the
+    audio buffer [capacity_samples] are allocated here, once: nothing is reallocated or copied later, and a recording that does not fit
+    raises ValueError and leaves the bank as it was.  See the module docstring for the clip index and the contract."""
+
+    def __init__(self, frame_size, clip_frames, frame_hop, hops_per_frame, hop, *, fps=30, sr=16000, capacity_frames, capacity_samples,
+                 storage="f32", device="cuda"):
+        s = _positive_int("frame_size", frame_size)
+        if s < 8 or s % 4:
+            raise ValueError(f"frame_size must be at least 8 and a multiple of 4, got {s}")
+        for name, v in (("clip_frames", clip_frames), ("frame_hop", frame_hop), ("hops_per_frame", hops_per_frame), ("hop", hop),
+                        ("capacity_frames", capacity_frames), ("capacity_samples", capacity_samples)):
+            _positive_int(name, v)
+        if not (fps > 0 and sr > 0):
+            raise ValueError("fps and sr must be positive")
+        if storage not in _STORAGE:
+            raise ValueError(f"storage must be 'f32' or 'u16', got {storage!r}")
+        self.frame_size, self.clip_frames, self.frame_hop, self.hops_per_frame, self.hop = s, clip_frames, frame_hop, hops_per_frame, hop
+        self.fps, self.sr, self.storage = fps, sr, storage
+        self.capacity_frames, self.capacity_samples = capacity_frames, capacity_samples
+        self.clip_samples = hops_per_frame * hop * clip_frames
+        self.frame_elems = (s // 8) ** 2
+        self.device = torch.device(device)
+        self.maps = torch.empty(capacity_frames, self.frame_elems, device=self.device, dtype=_STORAGE[storage][1])
+        self.audio = torch.empty(capacity_samples, device=self.device, dtype=torch.float32)
+        self.n_frames = self.n_samples = 0            # used part of the two buffers
+        self.recordings = []                          # per recording (first frame, first sample, frames, samples, clips)
+        self._clip_ends = []                          # running total of clips after each recording
+        self._tables = None                           # the same as CPU tensors, for batch()
+
+    # ---- the clip index: pure host arithmetic ---------------------------------------------------------
+    def __len__(self):
+        return self._clip_ends[-1] if self._clip_ends else 0
+
+    def locate(self, idx):
+        """Clip number -> (recording, k): clip k of the recording-th recording added."""
+        if isinstance(idx, bool) or not isinstance(idx, int) or not 0 <= idx < len(self):
+            raise IndexError(f"clip index {idx!r} is outside [0, {len(self)})")
+        r = bisect_right(self._clip_ends, idx)
+        return r, idx - (self._clip_ends[r - 1] if r else 0)
+
+    def clip_start(self, idx):
+        """Clip number -> (frame, sample): where the clip starts in the bank's two buffers."""
+        r, k = self.locate(idx)
+        f0, s0 = self.recordings[r][:2]
+        return f0 + k * self.frame_hop, s0 + clip_sample_start(k, self.frame_hop, self.fps, self.sr)
+
+    def count_clips(self, n_frames, n_samples):
+        return count_clips(n_frames, n_samples, self.clip_frames, self.frame_hop, self.clip_samples, self.fps, self.sr)
+
+    def _append(self, n_frames, n_samples, n_clips):
+        self.recordings.append((self.n_frames, self.n_samples, n_frames, n_samples, n_clips))
+        self._clip_ends.append(len(self) + n_clips)
+        self.n_frames += n_frames
+        self.n_samples += n_samples
+        self._tables = None
+
+    def _check_recording(self, audio, frames, maps, video_attention):
+        """Every refusal of add_recording, on shapes and the bank's fill alone -> (clips, frames used, samples used)."""
+        if (frames is None) == (maps is None):
+            raise ValueError("pass exactly one of frames= (ViT input frames) and maps= (per-frame maps at patch resolution)")
+        if not isinstance(audio, torch.Tensor) or audio.dim() != 1 or audio.dtype != torch.float32:
+            raise ValueError(f"audio must be a 1-D float32 tensor, got {getattr(audio, 'dtype', type(audio))} {tuple(getattr(audio, 'shape', ()))}")
+        s = self.frame_size
+        if frames is not None:
+            if video_attention is None:
+                raise ValueError("frames= needs video_attention=, the extractor that turns them into maps")
+            if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or tuple(frames.shape[1:]) != (3, s, s) or frames.dtype != torch.float32:
+                raise ValueError(f"frames must be float32 [N, 3, {s}, {s}], got {getattr(frames, 'dtype', type(frames))} "
+                                 f"{tuple(getattr(frames, 'shape', ()))}")
+            n = frames.shape[0]
+        else:
+            if video_attention is not None:
+                raise ValueError("video_attention= goes with frames=; maps= are stored as given")
+            if not isinstance(maps, torch.Tensor) or maps.dim() != 2 or maps.shape[1] != self.frame_elems or maps.dtype != torch.float32:
+                raise ValueError(f"maps must be float32 [N, {self.frame_elems}] (the {s // 8} x {s // 8} patch grid of {s} x {s} frames), got "
+                                 f"{getattr(maps, 'dtype', type(maps))} {tuple(getattr(maps, 'shape', ()))}")
+            n = maps.shape[0]
+        n_clips = self.count_clips(n, audio.shape[0])
+        if n_clips == 0:
+            raise ValueError(f"the recording ({n} frames, {audio.shape[0]} samples) holds no whole clip of {self.clip_frames} frames and "
+                             f"{self.clip_samples} samples")
+        used_f = (n_clips - 1) * self.frame_hop + self.clip_frames
+        used_s = clip_sample_start(n_clips - 1, self.frame_hop, self.fps, self.sr) + self.clip_samples
+        if self.n_frames + used_f > self.capacity_frames:
+            raise ValueError(f"capacity_frames={self.capacity_frames} exceeded: {self.n_frames} frames banked, the recording's clips use {used_f}")
+        if self.n_samples + used_s > self.capacity_samples:
+            raise ValueError(f"capacity_samples={self.capacity_samples} exceeded: {self.n_samples} samples banked, the recording's clips use {used_s}")
+        return n_clips, used_f, used_s
+
+    def add_recording(self, audio, *, frames=None, maps=None, video_attention=None):
+        """Bank one recording -> the number of clips it adds.  audio [L] f32, mono at `sr`, on the bank's device (a raw recording goes
+        through AudioTransform first).  Exactly one of
+          frames [N,3,S,S] f32, the ViT input after the frame transform, with video_attention=: the frames go through cls_attention and
+            maavss_vit_attn_maps_pass1, frames_per_launch at a time, straight into the map buffer.  The extractor's non-finite flag is
+            read once at the end (this call may synchronise); a non-finite map raises MaavssError and the recording is not added.
+          maps [N,(S//8)^2] f32 as pass 1 writes them: for callers with maps of their own.  They are stored as given, unchecked.
+        The crop is whatever the frames were given with: one crop per recording, fixed when it is banked, as in the reference's
+        attention-frame cache.  Frames and samples behind the recording's last whole clip are not kept."""
+        n_clips, used_f, used_s = self._check_recording(audio, frames, maps, video_attention)
+        u16 = self.storage == "u16"
+        if u16 or frames is not None:
+            _lib.require_cuda(audio, frames, maps, self.maps)
+        dst, st = self.maps[self.n_frames:self.n_frames + used_f], None
+        if frames is not None:
+            va, st = video_attention, stream_ptr()
+            flag = torch.zeros(1, device=self.device, dtype=torch.int32)
+            step = va.frames_per_launch
+            fmax = torch.empty(min(step, used_f), device=self.device, dtype=torch.float32)
+            tmp = torch.empty(min(step, used_f), self.frame_elems, device=self.device, dtype=torch.float32) if u16 else None
+            for f0 in range(0, used_f, step):
+                f1 = min(used_f, f0 + step)
+                att = va.cls_attention(frames[f0:f1])
+                small = tmp[:f1 - f0] if u16 else dst[f0:f1]
+                call("maavss_vit_attn_maps_pass1", ptr(att), ptr(small), ptr(fmax), f1 - f0, va.spec.heads, self.frame_elems, ptr(flag), st)
+                if u16:
+                    call("maavss_bank_pack_u16", ptr(small), ptr(dst[f0:f1]), small.numel(), st)
+            if int(flag.item()) != 0:
+                raise _lib.MaavssError(
+                    "ClipBank: non-finite attention maps -- an activation of the ViT left the range of its 16-bit storage format "
+                    f"(act_dtype={va.act_dtype!r}) or the input frames / weights hold inf or NaN; the recording was not added")
+        elif u16:
+            src = maps[:used_f].contiguous()
+            call("maavss_bank_pack_u16", ptr(src), ptr(dst), src.numel(), stream_ptr())
+        else:
+            dst.copy_(maps[:used_f])
+        self.audio[self.n_samples:self.n_samples + used_s].copy_(audio[:used_s])
+        self._append(used_f, used_s, n_clips)
+        return n_clips
+
+    def unpacked_maps(self, recording=None):
+        """The banked maps as f32 [frames, (S//8)^2] (a copy), of one recording or of all: what batch() normalises and upsamples."""
+        f0, n = (0, self.n_frames) if recording is None else (self.recordings[recording][0], self.recordings[recording][2])
+        part = self.maps[f0:f0 + n]
+        if self.storage == "f32" or n == 0:
+            return part.clone()
+        _lib.require_cuda(part)
+        out = torch.empty(n, self.frame_elems, device=self.device, dtype=torch.float32)
+        call("maavss_bank_unpack_u16", ptr(part), ptr(out), out.numel(), stream_ptr())
+        return out
+
+    # ---- batches ----------------------------------------------------------------------------------------
+    def check_indices(self, indices):
+        """Host-side validation of batch()'s indices (no device work) -> (frame starts int32 [B], sample starts int64 [B]), CPU tensors
+        in bank coordinates."""
+        if isinstance(indices, torch.Tensor):
+            if indices.is_cuda:
+                raise ValueError("indices must be a CPU sequence or tensor (they are checked on the host, like crop boxes)")
+            if indices.dim() != 1 or indices.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8):
+                raise ValueError(f"indices must be a 1-D integer tensor, got {indices.dtype} {tuple(indices.shape)}")
+            idx = indices.to(torch.int64)
+        else:
+            idx = list(indices)
+            if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
+                raise ValueError("indices must be integers")
+            idx = torch.tensor(idx, dtype=torch.int64)
+        if idx.numel() == 0:
+            raise ValueError("indices is empty")
+        if bool(((idx < 0) | (idx >= len(self))).any()):
+            raise IndexError(f"clip indices must be in [0, {len(self)}), got [{int(idx.min())}, {int(idx.max())}]")
+        if self._tables is None:
+            rec = torch.tensor(self.recordings, dtype=torch.int64)
+            ends = torch.tensor(self._clip_ends, dtype=torch.int64)
+            s_k = torch.tensor([clip_sample_start(k, self.frame_hop, self.fps, self.sr) for k in range(int(rec[:, 4].max()))], dtype=torch.int64)
+            self._tables = (ends, ends - rec[:, 4], rec[:, 0], rec[:, 1], s_k)
+        ends, firsts, frame0, sample0, s_k = self._tables
+        r = torch.bucketize(idx, ends, right=True)
+        k = idx - firsts[r]
+        return (frame0[r] + k * self.frame_hop).to(torch.int32), sample0[r] + s_k[k]
+
+    def batch(self, indices, *, attn_diff=False, out=None):
+        """The clips `indices` (a CPU sequence or integer tensor; duplicates allowed; anything outside [0, len) raises before any device
+        work) -> (attn [B,1,clip_frames,S,S] f32, audio [B, clip_samples] f32) on the current stream.  out=(attn, audio): buffers of
+        those shapes to fill (attn contiguous; audio with unit last stride, its rows may be longer than a clip).  The start tables
+        reach the device in one copy from pinned memory: no synchronisation."""
+        return self.cut(*self.check_indices(indices), attn_diff=attn_diff, out=out)
+
+    def cut(self, frame_start, sample_start, *, attn_diff=False, out=None):
+        """batch() behind its index check: the two CPU tables check_indices returned -> (attn, audio)."""
+        b, t, s, n =frame_start.numel(), self.clip_frames, self.frame_size, self.clip_samples
+        if out is None:
+            _lib.require_cuda(self.maps)
+            attn = torch.empty(b, 1, t, s, s, device=self.device, dtype=torch.float32)
+            audio = torch.empty(b, n, device=self.device, dtype=torch.float32)
+        else:
+            attn, audio = out
+            if (not isinstance(attn, torch.Tensor) or tuple(attn.shape) != (b, 1, t, s, s) or attn.dtype != torch.float32
+                    or not attn.is_contiguous()):
+                raise ValueError(f"out[0] must be a contiguous float32 {[b, 1, t, s, s]} tensor, got {getattr(attn, 'dtype', type(attn))} "
+                                 f"{tuple(getattr(attn, 'shape', ()))}")
+            if (not isinstance(audio, torch.Tensor) or tuple(audio.shape) != (b, n) or audio.dtype != torch.float32 or audio.stride(1) != 1
+                    or (b > 1 and audio.stride(0) < n)):
+                raise ValueError(f"out[1] must be a float32 {[b, n]} tensor with unit last stride and rows that do not overlap, got "
+                                 f"{getattr(audio, 'dtype', type(audio))} {tuple(getattr(audio, 'shape', ()))}")
+            _lib.require_cuda(self.maps, attn, audio)
+        # both tables in one copy through pinned memory, as Mixer stages its partners: a blocking copy on ClipPipeline's side stream would
+        # hold the host until the work queued in front of it had finished.  int64 sample starts first (8-byte aligned), then the frames
+        host = torch.cat([sample_start.view(torch.int32), frame_start])
+        staged = torch.empty(3 * b, device=self.device, dtype=torch.int32)
+        staged.copy_(host.pin_memory(), non_blocking=True)
+        rcp = torch.empty(b, device=self.device, dtype=torch.float32)
+        st = stream_ptr()
+        call("maavss_bank_attn_clips", ptr(self.maps), _STORAGE[self.storage][0], ptr(staged[2 * b:]), b, self.n_frames, t, s, s,
+             int(bool(attn_diff)), ptr(rcp), ptr(attn), st)
+        call("maavss_bank_audio_clips", ptr(self.audio), self.n_samples, ptr(staged), b, n, ptr(audio), audio.stride(0) if b > 1 else n, st)
+        return attn, audio
+
+    # ---- one file -----------------------------------------------------------------------------------------
+    def save(self, path):
+        """The used part of both buffers (CPU tensors), the per-recording lengths and every constructor argument, in one file."""
+        torch.save({"format": FORMAT, "version": FORMAT_VERSION, "frame_size": self.frame_size, "clip_frames": self.clip_frames,
+                    "frame_hop": self.frame_hop, "hops_per_frame": self.hops_per_frame, "hop": self.hop, "fps": self.fps, "sr": self.sr,
+                    "storage": self.storage, "capacity_frames": self.capacity_frames, "capacity_samples": self.capacity_samples,
+                    "recordings": torch.tensor([r[2:4] for r in self.recordings], dtype=torch.int64).reshape(-1, 2),
+                    "maps": self.maps[:self.n_frames].cpu(), "audio": self.audio[:self.n_samples].cpu()}, path)
+
+    @classmethod
+    def load(cls, path, device="cuda", *, frame_size=None, storage=None, capacity_frames=None, capacity_samples=None):
+        """A bank as save() wrote it (read with torch.load(weights_only=True)).  frame_size / storage: what the caller expects; a file
+        that says otherwise is refused.  capacity_*: default the stored fill, may be given larger."""
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(d, dict) or d.get("format") != FORMAT:
+            raise ValueError(f"{path}: not a ClipBank file (format {d.get('format') if isinstance(d, dict) else type(d).__name__!r})")
+        if d.get("version") != FORMAT_VERSION:
+            raise ValueError(f"{path}: version {d.get('version')!r} of the ClipBank format, this build reads version {FORMAT_VERSION}")
+        if frame_size is not None and frame_size != d["frame_size"]:
+            raise ValueError(f"{path}: frame_size {d['frame_size']} in the file, frame_size={frame_size} expected")
+        if storage is not None and storage != d["storage"]:
+            raise ValueError(f"{path}: storage {d['storage']!r} in the file, storage={storage!r} expected")
+        maps, audio = d["maps"], d["audio"]
+        cap_f = maps.shape[0] if capacity_frames is None else capacity_frames
+        cap_s = audio.shape[0] if capacity_samples is None else capacity_samples
+        if cap_f < maps.shape[0] or cap_s < audio.shape[0]:
+            raise ValueError(f"{path}: holds {maps.shape[0]} frames and {audio.shape[0]} samples, more than capacity_frames={cap_f} / "
+                             f"capacity_samples={cap_s}")
+        bank = cls(d["frame_size"], d["clip_frames"], d["frame_hop"], d["hops_per_frame"], d["hop"], fps=d["fps"], sr=d["sr"],
+                   capacity_frames=max(cap_f, 1), capacity_samples=max(cap_s, 1), storage=d["storage"], device=device)
+        if maps.dtype != bank.maps.dtype or maps.dim() != 2 or maps.shape[1] != bank.frame_elems or audio.dtype != torch.float32 or audio.dim() != 1:
+            raise ValueError(f"{path}: buffers {maps.dtype} {tuple(maps.shape)} / {audio.dtype} {tuple(audio.shape)} do not fit "
+                             f"storage {d['storage']!r} at frame_size {d['frame_size']}")
+        for n_f, n_s in d["recordings"].tolist():
+            n_clips = bank.count_clips(n_f, n_s)
+            if n_clips == 0 or bank.n_frames + n_f > maps.shape[0] or bank.n_samples + n_s > audio.shape[0]:
+                raise ValueError(f"{path}: the recording table does not fit the stored buffers")
+            bank._append(n_f, n_s, n_clips)
+        bank.maps[:bank.n_frames].copy_(maps[:bank.n_frames])
+        bank.audio[:bank.n_samples].copy_(audio[:bank.n_samples])
+        return bank

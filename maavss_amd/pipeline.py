@@ -15,14 +15,23 @@ AudioTransform) and `audio_length` (the samples per clip the STFT is to see) the
 at their own rate go through av_dataset.py:203-215 on the side stream in front of the STFT, into a per-slot clip buffer.
 With `mixer` (a Mixer built on the same STFT) the bare STFT call becomes the mixer's: x is the clip mixed with other clips of the batch
 (the interferers are the clips after the audio transform), y stays the clip's own STFT.
+With `bank` (a ClipBank) the batches come from attention maps and audio already resident on the device: `submit_clips(indices, seed)`
+cuts them on the side stream (no ViT, no frame or audio transform) in front of the same STFT / mixer call; `video_attention` may
+then be None.
 """
 import torch
 
 
 class ClipPipeline:
     def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None, audio_transform=None,
-                 audio_length=None, mixer=None):
+                 audio_length=None, mixer=None, bank=None):
         self.va, self.stft, self.t = video_attention, stft, clip_frames
+        if bank is not None:
+            if transform is not None or audio_transform is not None:
+                raise ValueError("transform= / audio_transform= do not go with bank=: a bank holds maps and audio that are already transformed")
+            if bank.clip_frames != clip_frames:
+                raise ValueError(f"the bank cuts clips of {bank.clip_frames} frames, the pipeline was given clip_frames={clip_frames}")
+        self.bank = bank
         self.transform = transform
         if audio_transform is None and audio_length is not None:
             raise ValueError("audio_length needs a ClipPipeline built with audio_transform=")
@@ -64,10 +73,11 @@ class ClipPipeline:
             if partners is not None or snr_db is not None:
                 raise ValueError("partners / snr_db need a ClipPipeline built with mixer=")
             return None, None
-        # the clips the mixer will see: `audio` itself, or the [B, audio_length] buffer the audio transform is about to fill
+        # the clips the mixer will see: `audio` itself (or its shape (B, L): submit_clips), or the [B, audio_length] buffer the audio
+        # transform is about to fill
         clips = audio if raw_audio is None else (raw_audio.shape[0], self.audio_length)
         if partners is None or snr_db is None:
-            drawn = self.mixer.sample(raw_audio.shape[0] if raw_audio is not None else audio.shape[0], torch.Generator().manual_seed(seed))
+            drawn = self.mixer.sample(clips.shape[0] if isinstance(clips, torch.Tensor) else clips[0], torch.Generator().manual_seed(seed))
             partners = drawn[0] if partners is None else partners
             snr_db = drawn[1] if snr_db is None else snr_db
         return self.mixer.check(clips, partners, snr_db)
@@ -82,6 +92,8 @@ class ClipPipeline:
         With a mixer, `partners` [B,K] int32 and `snr_db` [B] (CPU) choose the mixtures; by default
         mixer.sample(B, torch.Generator().manual_seed(seed)), which is also what mixer(audio, seed=seed) draws: a pipelined and a serial
         run see the same mixtures."""
+        if self.va is None:
+            raise ValueError("submit() needs a ClipPipeline built with a video_attention (a bank-fed one takes submit_clips())")
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
         slot = self.slots[self.head % self.depth]
         raw_audio = self.check_audio(audio, audio_sr)                        # everything is validated before any device work
@@ -125,6 +137,38 @@ class ClipPipeline:
             slot["ready"].record(self.side)
         self.head += 1
 
+    def submit_clips(self, indices, seed, *, attn_diff=False, partners=None, snr_db=None):
+        """Enqueue one batch cut from the bank: `indices` as ClipBank.batch takes them (CPU; checked before any device work), `seed`,
+        `partners` and `snr_db` as in submit().  On the side stream bank.batch fills the slot's buffers, then the STFT / mixer call and
+        the events are those of submit(); get() / release() do not change."""
+        if self.bank is None:
+            raise ValueError("submit_clips needs a ClipPipeline built with bank=")
+        assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
+        slot = self.slots[self.head % self.depth]
+        bank = self.bank
+        starts = bank.check_indices(indices)
+        b = starts[0].numel()
+        partners, snr_db = self.check_mix((b, bank.clip_samples), None, seed, partners, snr_db)
+        f, s = b * self.t, bank.frame_size
+        main = torch.cuda.current_stream()
+        produced = torch.cuda.Event()
+        produced.record(main)                               # recordings banked on the caller's stream just before this call
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(produced)
+            if slot["consumed"] is not None:
+                self.side.wait_event(slot["consumed"])
+            if slot["attn"] is None or slot["attn"].shape != (f, 1, s, s):
+                slot["attn"] = torch.empty(f, 1, s, s, device=bank.device, dtype=torch.float32)
+            if slot.get("clips") is None or slot["clips"].shape != (b, bank.clip_samples):
+                slot["clips"] = torch.empty(b, bank.clip_samples, device=bank.device, dtype=torch.float32)
+            _, audio = bank.cut(*starts, attn_diff=attn_diff, out=(slot["attn"].view(b, 1, self.t, s, s), slot["clips"]))
+            if self.mixer is not None:
+                slot["x"], slot["y"] = self.mixer(audio, partners, snr_db, seed=seed)
+            else:
+                slot["x"], slot["y"] = self.stft(audio, seed=seed)
+            slot["ready"].record(self.side)
+        self.head += 1
+
     def get(self):
         """(attention frames [B,1,T,H,W], x_stft, y_stft) of the oldest submitted batch; the current stream waits for them."""
         assert self.tail < self.head, "nothing submitted"
@@ -142,4 +186,5 @@ class ClipPipeline:
 
     def drain(self):
         self.side.synchronize()
-        self.va.check_finite()
+        if self.va is not None:                 # a bank-fed pipeline has no extractor: its maps were checked when they were banked
+            self.va.check_finite()
