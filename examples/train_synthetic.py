@@ -12,6 +12,7 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --mix 2 --mix_snr 0 10                 # mix-and-separate: every clip + 2 others of the batch at 0..10 dB
     python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
     python examples/train_synthetic.py --val 2                                # every 2 steps: held-out loss and LSD, a checkpoint on improvement
+    python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
     python examples/train_synthetic.py --bank 8 [--bank_storage u16]          # the ViT once per recording: maps and audio of 8 recordings in
                                                                               # HBM (ClipBank), every batch cut from them by clip index
 """
@@ -149,8 +150,20 @@ def main():
             pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345)
         else:
             g_train, g = g, torch.Generator().manual_seed(12345)
-            pipe.submit(*batch(), seed=12345, **sr_arg)
+            frames_v, audio_v = batch()
+            pipe.submit(frames_v, audio_v, seed=12345, **sr_arg)
             g = g_train
+            if mixer is not None and not a.raw_audio:
+                # what kind of error the held-out mixtures hold before any separation (BSS-eval, maavss_amd.bss_eval_metrics): the same
+                # seed draws the partners and ratios the pipeline's mixer call draws.  The Mixer has no output for the interferers'
+                # waveform: `mixture - audio_v` is a torch subtraction.  The model's own output is scored the same way once it is a
+                # waveform: Validator(bss_filter=...).add_recording(enhancer, mixture, clean, attn=..., others=...)
+                mixture = mixer(audio_v, seed=12345, return_mixture=True)[2]
+                bss = maavss_amd.Validator(model, bss_filter=512)
+                bss.add_waves(mixture, audio_v, others=mixture - audio_v)
+                r = bss.result()
+                print(f"held-out mixtures, 512-tap BSS-eval over {r['sdr_db_n_finite']} clips: SDR {r['sdr_db']:.2f} dB  SIR {r['sir_db']:.2f} dB  "
+                      f"SAR {r['sar_db']:.2f} dB", flush=True)
         held_out = tuple(t.clone() for t in pipe.get())
         pipe.release()
         validator = maavss_amd.Validator(model, loss_coeff=0.001, num_seq=ns)

@@ -405,6 +405,42 @@ int64_t maavss_stoi_ws_bytes(int64_t rows, int64_t n);
 int maavss_stoi(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t rows, int64_t n, double* out, void* ws,
                 int64_t ws_bytes, void* stream);
 
+/* ---- EXTENSION: BSS-eval SDR, SIR and SAR against known sources (maavss_amd.bss_eval_metrics, Validator(bss_filter=...)) ----------
+ * maavss_bss_eval: per row, the estimate e[0..n), the target s_0[0..n) (ref) and K >= 0 other sources s_1..s_K (others), all f32, and a
+ * time-invariant distortion filter of L taps (Vincent, Gribonval & Fevotte 2006).  T = n + L - 1; every signal is zero outside [0, n).
+ * Everything is f64 over the f32 data in a fixed order: no floating-point atomics, two runs give identical bytes, and a row's bytes do not
+ * depend on the other rows of the call.  Added without a version bump.  tests/bss_twin.py is the float64 restatement.
+ *   live      the target is live; another source is live when the f64 sum of its exact squares is not 0 (an all-zero source, an empty
+ *             Mixer slot, is left out exactly).  J = the number of live sources
+ *   lags      A_j[m, t] = s_j[m - t], m in [0, T), t in [0, L); A = [A_0 .. A_{J-1}] over the live sources in their order
+ *   target    c_t solves (A_0^T A_0) c_t = A_0^T e; p_t = A_0 c_t
+ *   full      c solves (A^T A) c = A^T e; p = A c.  With J = 1 the second solve is not run and p is p_t itself
+ *   Gram      every entry of A^T A and of A^T e is an f64 sum of exact products of f32 samples, the auto- and cross-correlations at the
+ *             lags -(L-1)..L-1; the matrix is block Toeplitz and is built from them.  It is factored by Cholesky (one factorisation:
+ *             the leading L x L block of the factor is the factor of A_0^T A_0)
+ *   sums      over m in [0, T), e zero-extended, each accumulated directly from the materialised projections, never as a difference of
+ *             quadratic forms:  S_tt = sum p_t^2, S_ee = sum (e - p_t)^2, S_ii = sum (p - p_t)^2, S_aa = sum (e - p)^2, S_pp = sum p^2
+ *   scores    sdr_db = 10 log10(S_tt / S_ee), sir_db = 10 log10(S_tt / S_ii), sar_db = 10 log10(S_pp / S_aa).  No epsilon: with J = 1
+ *             S_ii is exactly 0, sir_db is +inf and sar_db equals sdr_db bit for bit
+ *   status    0 ok; 1 a sample of e or of any source is non-finite; 2 the target is silent; 3 a Cholesky pivot is not positive or not
+ *             finite.  With a status the five sums and the three scores are NaN; n_sources is 0 for 1 and 2, J for 3.  A Gram matrix that
+ *             is rank-deficient without an exactly silent source (two identical sources) gives status 3 or whatever the arithmetic gives
+ * Deviations from the usual Python package (bss_eval_sources), stated: the silent-source rule; NaN and a status where the package falls
+ * back to a least-squares solve; no permutation search (the target is known); no framewise variant.
+ * out [rows][10] f64: S_tt, S_ee, S_ii, S_aa, S_pp, sdr_db, sir_db, sar_db, n_sources, status.
+ * 0 <= K <= 3, 1 <= L <= 512, n >= (K + 1) L (otherwise there are more unknowns than equations), n < 2^31, rows <= 65535.  Strides in
+ * elements, >= 0, rows may overlap; the row strides are ignored when rows = 1, others_src_stride (between the sources of one row) when
+ * K < 2; others may be null when K = 0; samples are contiguous and the pointers need 4-byte alignment only.
+ * ws: maavss_bss_eval_ws_bytes(rows, n, K, L) bytes (0 for invalid arguments), 8-byte aligned: per row 8 ints, per (signal, chunk of 2048
+ * samples) two doubles, per (ordered pair, chunk) and per ordered pair L lags, the matrix of (64 nbt + 64) x 64 nbt doubles with
+ * nbt = ceil((K + 1) L / 64) (34.6 MB at 2048 unknowns), the nbt factored diagonal tiles (32 KB each), 2 x 64 nbt coefficients and
+ * 5 doubles per 1024 outputs.
+ * Launches: screen, plan, corr, corr_sum, gram, per tile column {panel, update}, backsolve, fir, finalize = 7 + 2 nbt. */
+int64_t maavss_bss_eval_ws_bytes(int64_t rows, int64_t n, int K, int L);
+int maavss_bss_eval(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, const float* others,
+                    int64_t others_row_stride, int64_t others_src_stride, int K, int64_t rows, int64_t n, int L, double* out, void* ws,
+                    int64_t ws_bytes, void* stream);
+
 /* K18 helper, EXTENSION (the reference is single-device): bf16 wire format of the data-parallel gradient all-reduce -- a bucket of
  * the flat f32 gradient buffer is rounded to bf16 (round-to-nearest-even) for the collective and widened back into the f32 master
  * buffer afterwards (trainer.GradSync(wire_dtype="bf16")).  n a multiple of 8, buffers 16-byte aligned. */

@@ -19,6 +19,7 @@ from .mixer import Mixer  # noqa: F401
 from .tensor_stats import ModelWatch, TensorStats, plan_chunks  # noqa: F401
 from .quality import Validator, plan_wave_chunks, spectrum_metrics, wave_metrics  # noqa: F401
 from .stoi import stoi_metrics  # noqa: F401
+from .bss import bss_eval_metrics  # noqa: F401
 from .clip_bank import ClipBank  # noqa: F401
 
 from . import attn_cache  # noqa: F401

@@ -9,7 +9,8 @@ example is judged by (csrc/quality_metrics.hip: f64 sums of the f32 data in a fi
 * `wave_metrics`     -- per row of est [B, L] against ref [B, L]: Sxx, Syy, Sxy, See, Srr, SNR, SI-SDR, segmental SNR
 * `spectrum_metrics` -- per row of pred [B, 2, T, F] against tgt: squared-error sum and log-spectral distance
 * `Validator`        -- an additive device accumulator of both over batches, clips and recordings; `result()` makes the one copy;
-                        with `intelligibility_sr=` also of STOI and ESTOI per clip (maavss_amd/stoi.py, csrc/stoi.hip)
+                        with `intelligibility_sr=` also of STOI and ESTOI per clip (maavss_amd/stoi.py, csrc/stoi.hip), with
+                        `bss_filter=` also of BSS-eval SDR, SIR and SAR against known other sources (maavss_amd/bss.py, csrc/bss_eval.hip)
 
 Definitions (include/maavss.h states them next to the entry points; tests/quality_twin.py is their float64 restatement):
   snr_db = 10 log10(Sxx / See), si_sdr_db = 10 log10(alpha^2 Sxx / Srr) with alpha = Sxy / Sxx and Srr = sum (est - alpha ref)^2 summed
@@ -20,6 +21,7 @@ Nothing here synchronises with the host before `Validator.result()`.
 import torch
 
 from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr, workspace
+from .bss import BSS_COLUMNS, BSS_DB, BSS_MAX_FILTER, bss_eval_metrics
 from .stoi import stoi_metrics
 from .trainer import sliding_windows
 
@@ -122,6 +124,9 @@ _ACC_LEN = 2 * len(_SUMS) + 5 * len(WAVE_DB) * len(_GROUPS)
 # the second accumulator, only with intelligibility_sr: the same five numbers for stoi and estoi of the same three groups
 _INTEL = ("stoi", "estoi")
 _INTEL_LEN = 5 * len(_INTEL) * len(_GROUPS)
+# the third accumulator, only with bss_filter: the same five numbers for sdr_db, sir_db and sar_db of the same three groups
+_BSS_LEN = 5 * len(BSS_DB) * len(_GROUPS)
+_BSS0 = BSS_COLUMNS.index("sdr_db")
 
 
 class Validator:
@@ -141,10 +146,15 @@ class Validator:
     The accumulator is one small f64 device tensor (`.acc`) of sums and counts only, so it is additive: the element-wise sum of the
     accumulators of several ranks is the accumulator of their data.  `add_*` enqueue kernels on the current stream and never wait."""
 
-    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10, intelligibility_sr=None):
+    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10, intelligibility_sr=None, bss_filter=None):
         """intelligibility_sr: the sample rate of the waves given to add_waves / add_recording; with it they also add STOI and ESTOI
         (maavss_amd.stoi_metrics) of the estimate, of the noisy input and of estimate minus noisy per clip, into a second small
-        accumulator (`.acc_intel`), and result() gains their keys.  None (the default): nothing of that is launched or reported."""
+        accumulator (`.acc_intel`), and result() gains their keys.  None (the default): nothing of that is launched or reported.
+        bss_filter: the length (1..512 taps) of the BSS-eval distortion filter; with it add_waves / add_recording also add sdr_db, sir_db
+        and sar_db (maavss_amd.bss_eval_metrics, against the `others` they are given) of the same three groups into a third accumulator
+        (`.acc_bss`), and result() gains their keys.  None (the default): nothing of that is launched or reported."""
+        if bss_filter is not None and (isinstance(bss_filter, bool) or not isinstance(bss_filter, int) or not 1 <= bss_filter <= BSS_MAX_FILTER):
+            raise ValueError(f"bss_filter must be None or an integer in 1..{BSS_MAX_FILTER} (taps), got {bss_filter!r}")
         if intelligibility_sr is not None and (isinstance(intelligibility_sr, bool) or not isinstance(intelligibility_sr, int)
                                                or intelligibility_sr < 1):
             raise ValueError(f"intelligibility_sr must be None or a positive integer (samples per second), got {intelligibility_sr!r}")
@@ -157,8 +167,10 @@ class Validator:
         self.model, self.loss_coeff, self.num_seq = model, float(loss_coeff), int(num_seq)
         self.seg_len, self.lsd_floor = int(seg_len), float(lsd_floor)
         self.intelligibility_sr = intelligibility_sr
+        self.bss_filter = bss_filter
         self.acc = None
         self.acc_intel = None        # with intelligibility_sr: the tail of the allocation `acc` heads, so that result() makes one copy
+        self.acc_bss = None          # with bss_filter: the tail after that
         self._buf = None
         self.best = None
 
@@ -170,11 +182,16 @@ class Validator:
     def _acc(self, dev):
         if self.acc is None:
             extra = 0 if self.intelligibility_sr is None else _INTEL_LEN
-            self._buf = torch.zeros(_ACC_LEN + extra, dtype=torch.float64, device=dev)
+            self._buf = torch.zeros(self._buf_len(), dtype=torch.float64, device=dev)
             self.acc = self._buf[:_ACC_LEN]
             if extra:
-                self.acc_intel = self._buf[_ACC_LEN:]
+                self.acc_intel = self._buf[_ACC_LEN:_ACC_LEN + extra]
+            if self.bss_filter is not None:
+                self.acc_bss = self._buf[_ACC_LEN + extra:]
         return self.acc
+
+    def _buf_len(self):
+        return _ACC_LEN + (0 if self.intelligibility_sr is None else _INTEL_LEN) + (0 if self.bss_filter is None else _BSS_LEN)
 
     def _slot(self, kind, group=None):
         if group is None:
@@ -212,9 +229,12 @@ class Validator:
         for _, xa, xv, ya, yv in sliding_windows(x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, self.num_seq):
             self.add_windows(xa, xv, ya, yv)
 
-    def add_waves(self, est, ref, noisy=None):
+    def add_waves(self, est, ref, noisy=None, others=None):
         """Per-row wave metrics of est against ref, each row one clip; with `noisy` (the unprocessed input of the same rows) also its own
-        metrics against ref and, per clip, estimate minus noisy: the improvements (SNRi, SI-SDRi, segmental SNRi)."""
+        metrics against ref and, per clip, estimate minus noisy: the improvements (SNRi, SI-SDRi, segmental SNRi).  `others` ([B, L] or
+        [B, K, L], the other sources of each row's mixture) is read only with bss_filter."""
+        if others is not None and self.bss_filter is None:
+            raise ValueError("others is given but this Validator was built without bss_filter")
         m = wave_metrics(est, ref, self.seg_len)["raw"]
         self._acc(m.device)
         st = stream_ptr()
@@ -235,10 +255,19 @@ class Validator:
                 sn = stoi_metrics(noisy, ref, self.intelligibility_sr)["raw"]
                 call("maavss_metric_add_classes", ptr(sn), None, b, cols, k, ptr(slot["noisy"]), st)
                 call("maavss_metric_add_classes", ptr(s), ptr(sn), b, cols, k, ptr(slot["gain"]), st)
+        if self.bss_filter is not None:
+            s = bss_eval_metrics(est, ref, others, self.bss_filter)["raw"]
+            cols, k = s.shape[1], len(BSS_DB)
+            slot = {g: self.acc_bss[5 * k * i:5 * k * (i + 1)] for i, g in enumerate(_GROUPS)}
+            call("maavss_metric_add_classes", ptr(s[:, _BSS0:]), None, b, cols, k, ptr(slot["est"]), st)
+            if noisy is not None:
+                sn = bss_eval_metrics(noisy, ref, others, self.bss_filter)["raw"]
+                call("maavss_metric_add_classes", ptr(sn[:, _BSS0:]), None, b, cols, k, ptr(slot["noisy"]), st)
+                call("maavss_metric_add_classes", ptr(s[:, _BSS0:]), ptr(sn[:, _BSS0:]), b, cols, k, ptr(slot["gain"]), st)
 
-    def add_recording(self, enhancer, noisy, clean, frames=None, attn=None):
+    def add_recording(self, enhancer, noisy, clean, frames=None, attn=None, others=None):
         """Enhance `noisy` [L] with `enhancer(noisy, frames= | attn=)` -> (wave, start) and measure the estimate and the noisy input against
-        clean[start : start + len(wave)], the span the estimate covers."""
+        clean[start : start + len(wave)], the span the estimate covers; `others` ([L] or [K, L], with bss_filter) is cut to the same span."""
         self._check_eval()
         if enhancer.model is not self.model:
             raise ValueError("the Enhancer wraps another model than this Validator")
@@ -249,7 +278,11 @@ class Validator:
         n = wave.shape[0]
         if clean.shape[0] < start + n:
             raise ValueError(f"clean has {clean.shape[0]} samples, the estimate covers [{start}, {start + n})")
-        self.add_waves(wave, clean[start:start + n], noisy=noisy[start:start + n])
+        if others is not None:
+            if not isinstance(others, torch.Tensor) or others.dim() not in (1, 2) or others.shape[-1] < start + n:
+                raise ValueError(f"others must be [L] or [K, L] and cover [{start}, {start + n}), got {getattr(others, 'shape', type(others))}")
+            others = others[..., start:start + n][None]
+        self.add_waves(wave, clean[start:start + n], noisy=noisy[start:start + n], others=others)
 
     def result(self):
         """The one device-to-host copy (it waits for the stream) -> dict:
@@ -258,10 +291,13 @@ class Validator:
         over the clips whose value is finite) and m_n_finite / _n_posinf / _n_neginf / _n_nan; with noisy inputs also noisy_m (and its
         counts) and m_improvement = the mean over clips of estimate minus noisy; n_clips.  A quantity nothing was added to is NaN.
         With intelligibility_sr also stoi, estoi, noisy_stoi, noisy_estoi, stoi_improvement, estoi_improvement (always all six) and
-        their _n_finite / _n_nan counts: a clip without a 384 ms segment, or with a non-finite sample, counts as NaN."""
+        their _n_finite / _n_nan counts: a clip without a 384 ms segment, or with a non-finite sample, counts as NaN.
+        With bss_filter also sdr_db, sir_db, sar_db, their noisy_ and _improvement forms (always all nine) and the four counts of each:
+        a clip with a status (a non-finite sample, a silent target, a pivot that is not positive) counts as NaN, one without another
+        live source has sir_db = +inf."""
         nan = float("nan")
         if self._buf is None:
-            h = [0.0] * (_ACC_LEN + (0 if self.intelligibility_sr is None else _INTEL_LEN))
+            h = [0.0] * self._buf_len()
         else:
             h = self._buf.cpu().tolist()
 
@@ -291,6 +327,14 @@ class Validator:
                     key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
                     out[key] = ratio(s, nf)
                     out.update({f"{key}_n_finite": int(nf), f"{key}_n_nan": int(nnan)})
+        if self.bss_filter is not None:
+            for group in _GROUPS:
+                for name in BSS_DB:
+                    s, nf, npos, nneg, nnan = h[o:o + 5]
+                    o += 5
+                    key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
+                    out[key] = ratio(s, nf)
+                    out.update({f"{key}_n_finite": int(nf), f"{key}_n_posinf": int(npos), f"{key}_n_neginf": int(nneg), f"{key}_n_nan": int(nnan)})
         return out
 
     def improved(self, result):
