@@ -15,6 +15,8 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
     python examples/train_synthetic.py --bank 8 [--bank_storage u16]          # the ViT once per recording: maps and audio of 8 recordings in
                                                                               # HBM (ClipBank), every batch cut from them by clip index
+    python examples/train_synthetic.py --figures 2 [--figures-dir figures]    # every 2 steps the reference's callback images as PNGs
+                                                                              # (maavss_amd.CallbackFigures: train_avse_frames.py:191-215)
 """
 import argparse
 import os
@@ -60,6 +62,10 @@ def main():
                     help="bank R synthetic recordings of 4 clips once (ViT + audio, maavss_amd.ClipBank: the reference's attn_frames_path / "
                          "use_audio_memmap), then draw every batch by clip index from a seeded permutation: no ViT in the step")
     ap.add_argument("--bank_storage", choices=("f32", "u16"), default="f32", help="with --bank: 4 or 2 bytes per map value")
+    ap.add_argument("--figures", type=int, default=0, metavar="N",
+                    help="every N steps (the reference's cb_freq), run the step with collect=True and make the callback's images on the "
+                         "device (maavss_amd.CallbackFigures), then write them as PNGs")
+    ap.add_argument("--figures-dir", default="figures", metavar="D", help="with --figures: where the PNGs go")
     a = ap.parse_args()
     if a.bank and (a.raw_video or a.raw_audio or a.overfit):
         ap.error("--bank holds transformed frames' maps and 16 kHz audio: it does not go with --raw_video, --raw_audio or --overfit")
@@ -74,6 +80,7 @@ def main():
     model = maavss_amd.AV_Fusion_Model_Frames([b, 2, hpf * nf, n_bins], [b, 1, nf, w, w], hpf, precise=a.precise).to(dev).train()
     step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip)
     watch = maavss_amd.ModelWatch(step, log_freq=a.watch) if a.watch else None
+    figures = maavss_amd.CallbackFigures(stft) if a.figures else None
     transform = None
     if a.raw_video:
         h0, w0 = (int(v) for v in a.raw_video.lower().split("x"))
@@ -172,7 +179,16 @@ def main():
     for i in range(a.steps):
         submit(0 if a.overfit else i + 1)                                # extraction of the next batch: side stream
         attn, x_stft, y_stft = pipe.get()                        # [B,1,T,H,W], [B,2,T_a,F] x 2
-        losses = step.sliding_window_step(x_stft, y_stft, attn, attn, nf, hpf)
+        if figures is not None and i % a.figures == 0:
+            # train_avse_frames.py:143-148, 173-177, 191-215: the stitched outputs, then the images of clip 0 -- launches only; the
+            # copies happen in save_png.  (The synthetic clips keep no video next to their attention frames: two strips, not three.)
+            losses, output_stft, output_attn = step.sliding_window_step(x_stft, y_stft, attn, attn, nf, hpf, collect=True)
+            logs = figures(y_stft, output_stft, attn, output_attn)
+            paths = maavss_amd.save_png(logs, a.figures_dir, i)
+            print(f"step {i}: {len(paths)} images in {a.figures_dir}/ (" + ", ".join(f"{k} {tuple(logs[k].shape)}" for k in maavss_amd.figures.IMAGE_KEYS)
+                  + f"); audio_input {tuple(logs['audio_input'].shape)}, audio_output {tuple(logs['audio_output'].shape)}", flush=True)
+        else:
+            losses = step.sliding_window_step(x_stft, y_stft, attn, attn, nf, hpf)
         pipe.release()
         logs = watch.after_step() if watch is not None else None
         if i % a.log_every == 0 or i == a.steps - 1:

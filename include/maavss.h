@@ -656,6 +656,52 @@ int maavss_bank_attn_clips(const void* maps, int storage, const int32_t* clip_st
 int maavss_bank_audio_clips(const float* bank, int64_t n_samples, const int64_t* clip_start, int64_t n_clips, int64_t L, float* out,
                             int64_t ld_out, void* stream);
 
+/* ---- the training callback's images (maavss_amd.figures; train_avse_frames.py:191-215) ----------------------------------------------
+ * RGBA bytes made on the device, defined pixel for pixel by matplotlib's colour mapping; tests/figures_twin.py restates every definition
+ * below in float64.  No entry point allocates, synchronises or uses an atomic; two runs give the same bytes.  Additive symbols (nothing
+ * existing changed meaning).
+ *
+ * What imshow does to an array (utilities.py:336-350 plt.imshow(y_stft_ex[0].T), :316 imshow(y_img, vmin=-1, vmax=1), and the image
+ * Axes.specgram makes, :398, :409): cm.viridis(Normalize(vmin, vmax)(np.ma.masked_invalid(x.astype(float64))), bytes=True).
+ * x: n_img images of H x W, dtype 0 = float32, 1 = float64, element (n, r, c) at x[n * sn + r * sh + c * sw] (element strides >= 0: a
+ * view needs no copy).  maavss_viridis_range: range[2 n], range[2 n + 1] = minimum and maximum over the finite elements of image n
+ * (+inf, -inf when it has none), f64.  maavss_viridis_image: per element u = (double(x) - vmin) / (vmax - vmin) in f64 (u = 0 when
+ * vmax == vmin), pixel = LUT[clamp(trunc(256 u), 0, 255)] with alpha 255, LUT = matplotlib's viridis as bytes (csrc/viridis_lut.h); a
+ * non-finite element gives (0, 0, 0, 0).  vmin / vmax of image n are range[2 n], range[2 n + 1] (device memory, e.g. what
+ * maavss_viridis_range wrote) unless bit 0 / bit 1 of `fixed` takes them from the arguments (fixed = 3: range may be null).
+ * transpose = 1: the image is x's transpose (W rows of H); flip_rows = 1: its rows from the last to the first; then every pixel is
+ * repeated sy x sx times (nearest, integers in 1 .. 64).  out uint8 [n_img][Hi sy][Wi sx][4], 4-byte aligned; four pixels per
+ * 16-byte store when it is 16-byte aligned (pixel by pixel otherwise, and for the last pixels of an output whose count is no multiple
+ * of four).  One launch each. */
+int maavss_viridis_range(const void* x, int dtype, int64_t n_img, int64_t H, int64_t W, int64_t sn, int64_t sh, int64_t sw,
+                         double* range, void* stream);
+int maavss_viridis_image(const void* x, int dtype, int64_t n_img, int64_t H, int64_t W, int64_t sn, int64_t sh, int64_t sw,
+                         const double* range, int fixed, double vmin, double vmax, int transpose, int flip_rows, int sy, int sx,
+                         void* out, void* stream);
+/* The two arrays utilities.plot_waveform_specgram (utilities.py:386-416) hands to imshow through Axes.specgram(x, mode='magnitude') and
+ * (mode='phase') with matplotlib's defaults, in f64 throughout.  wave: rows x L f32, row r at wave + r * stride (stride >= 0, rows may
+ * overlap; 4-byte aligned).  nfft a power of two in 32 .. 1024, 0 <= noverlap < nfft.  A row shorter than nfft is zero-padded to it;
+ * n = (max(L, nfft) - noverlap) / (nfft - noverlap) segments (maavss_specgram_segments; 0 for arguments maavss_specgram refuses),
+ * segment i from sample i (nfft - noverlap), times np.hanning(nfft) (the symmetric window), no detrending, one-sided transform F.
+ * mag_db = 20 log10(|F| / sum(w)); phase = np.unwrap(angle(F)) along frequency: dd = diff(p), m = mod(dd + pi, 2 pi) - pi with m = pi
+ * where m == -pi and dd > 0, the correction m - dd zeroed where |dd| < pi, its cumulative sum (in bin order) added.  Both
+ * [rows][nfft / 2 + 1][n] f64 with row 0 the Nyquist bin (specgram flips before imshow).  A silent segment gives -inf dB and phase 0;
+ * a non-finite sample makes its segments NaN; samples equal to -0.0 are outside the contract (angle(-0) = pi).  One launch, one
+ * workgroup per (row, segment). */
+int64_t maavss_specgram_segments(int64_t rows, int64_t L, int nfft, int noverlap);
+int maavss_specgram(const float* wave, int64_t stride, int64_t rows, int64_t L, int nfft, int noverlap, double* mag_db, double* phase,
+                    void* stream);
+/* utilities.video_frames_image with generate_filmstrip(..., resize=False) (utilities.py:286-326, 230-245) as one image.  y_attn, yh_attn
+ * [T][H][W] f32, video [3][T][H][W] f32 or null, all contiguous.  Per tensor, in f32 as the reference forms it: s = 1 / (max + 1e-7),
+ * v s, clipped to [0, 1]; the inputs are NOT modified (the reference scales its arguments in place).  max is the tensor's maximum
+ * with NaNs ignored (torch.max would return the NaN); a NaN element gives the pixel (0, 0, 0, 0).  Attention pixels: the colour map
+ * with vmin = -1, vmax = 1 (the reference's imshow arguments), so the maps use its upper half; video pixels: (trunc(255 r),
+ * trunc(255 g), trunc(255 b), 255), what imshow does with float RGB.  out uint8 [R H][T W][4], 4-byte aligned (16-byte stores when 16-byte aligned): frame t at columns
+ * t W .. t W + W - 1 (frames may be rectangular; the reference's indexing is right for square ones only), strips from the top: video,
+ * y, yh (R = 3), or y, yh (R = 2, video null).  maxes: 192 floats of workspace (64 partial maxima per tensor).  Two launches. */
+int maavss_filmstrip(const float* y_attn, const float* yh_attn, const float* video, int T, int H, int W, float* maxes, void* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
