@@ -17,6 +17,8 @@ stream (ClipPipeline).
                                                                               # HBM (ClipBank), every batch cut from them by clip index
     python examples/train_synthetic.py --figures 2 [--figures-dir figures]    # every 2 steps the reference's callback images as PNGs
                                                                               # (maavss_amd.CallbackFigures: train_avse_frames.py:191-215)
+    python examples/train_synthetic.py --audio_loss compressed [--compress 0.3 --loss_mix 0.3]    # the power-law compressed spectral loss
+                                                                              # as the audio term (goes with --val, --mix and --overfit)
 """
 import argparse
 import os
@@ -65,6 +67,12 @@ def main():
     ap.add_argument("--figures", type=int, default=0, metavar="N",
                     help="every N steps (the reference's cb_freq), run the step with collect=True and make the callback's images on the "
                          "device (maavss_amd.CallbackFigures), then write them as PNGs")
+    ap.add_argument("--audio_loss", choices=("mse", "compressed"), default="mse",
+                    help="the audio term of the loss: the reference's MSE of the STFT planes, or the power-law compressed spectral loss "
+                         "(maavss_amd.SpectralLoss: TrainStep(audio_loss=...), and with --val Validator(audio_loss=...))")
+    ap.add_argument("--compress", type=float, default=0.3, metavar="C", help="with --audio_loss compressed: the exponent, in (0, 1]")
+    ap.add_argument("--loss_mix", type=float, default=0.3, metavar="L",
+                    help="with --audio_loss compressed: the weight of the complex term, in [0, 1]; the magnitude term gets 1 - L")
     ap.add_argument("--figures-dir", default="figures", metavar="D", help="with --figures: where the PNGs go")
     a = ap.parse_args()
     if a.bank and (a.raw_video or a.raw_audio or a.overfit):
@@ -78,7 +86,8 @@ def main():
     extractor = maavss_amd.VideoAttention(path_to_weights="dino_deitsmall8_pretrain.pth")      # random init when absent (no network)
     stft = maavss_amd.STFT(a.fft_len, hop, noise_std=0.1, device=dev)
     model = maavss_amd.AV_Fusion_Model_Frames([b, 2, hpf * nf, n_bins], [b, 1, nf, w, w], hpf, precise=a.precise).to(dev).train()
-    step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip)
+    audio_loss = maavss_amd.SpectralLoss(a.compress, a.loss_mix) if a.audio_loss == "compressed" else None
+    step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip, audio_loss=audio_loss)
     watch = maavss_amd.ModelWatch(step, log_freq=a.watch) if a.watch else None
     figures = maavss_amd.CallbackFigures(stft) if a.figures else None
     transform = None
@@ -173,7 +182,7 @@ def main():
                       f"SAR {r['sar_db']:.2f} dB", flush=True)
         held_out = tuple(t.clone() for t in pipe.get())
         pipe.release()
-        validator = maavss_amd.Validator(model, loss_coeff=0.001, num_seq=ns)
+        validator = maavss_amd.Validator(model, loss_coeff=0.001, num_seq=ns, audio_loss=audio_loss)
         val_dir = tempfile.TemporaryDirectory()
     submit(0)
     for i in range(a.steps):
@@ -193,7 +202,8 @@ def main():
         logs = watch.after_step() if watch is not None else None
         if i % a.log_every == 0 or i == a.steps - 1:
             clip = "" if a.clip is None else f"  |g| {step.opt.grad_norm.item():.4g}  scale {step.opt.clip_scale.item():.4g}"
-            print(f"step {i}: a_loss {losses[0].item():.5f}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}", flush=True)
+            parts = "" if audio_loss is None else "  (magnitude {:.5f}, complex {:.5f})".format(*step.loss_parts.tolist())
+            print(f"step {i}: a_loss {losses[0].item():.5f}{parts}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}", flush=True)
         if validator is not None and (i + 1) % a.val == 0:
             attn_v, x_v_stft, y_v_stft = held_out
             model.eval()
@@ -202,9 +212,10 @@ def main():
             res = validator.result()
             model.train()
             print(f"step {i}: validation {res}", flush=True)
-            if validator.improved(res):
-                maavss_amd.save_checkpoint(model.state_dict(), step.opt.state_dict(), i, res["val_loss"], "synthetic-best", val_dir.name)
-                print(f"step {i}: val_loss {res['val_loss']:.5f} improved: checkpoint saved", flush=True)
+            key = "val_loss" if audio_loss is None else "val_objective"          # the loss the step trains on
+            if validator.improved(res, key=key):
+                maavss_amd.save_checkpoint(model.state_dict(), step.opt.state_dict(), i, res[key], "synthetic-best", val_dir.name)
+                print(f"step {i}: {key} {res[key]:.5f} improved: checkpoint saved", flush=True)
         if logs is not None:
             # with wandb: wandb.log({k: wandb.Histogram(np_histogram=v) for k, v in logs.items() if not k.startswith("nonfinite/")})
             bad = [k for k in logs if k.startswith("nonfinite/")]

@@ -376,6 +376,40 @@ int maavss_sqerr_rows(const float* pred, const float* tgt, int64_t B, int64_t n,
 int maavss_metric_add_sum(const double* vals, int64_t n, int64_t stride, double weight, double* acc, void* stream);
 int maavss_metric_add_classes(const double* vals, const double* minus, int64_t n, int64_t stride, int cols, double* acc, void* stream);
 
+/* ---- EXTENSION: power-law compressed spectral loss and its gradient (maavss_amd.SpectralLoss, TrainStep(audio_loss=...)) -------
+ * An audio objective beside the plain MSE of mse_pair: compressed magnitudes plus compressed complex coefficients, per bin, on any
+ * number of frames and without an inverse STFT.  Added without a version bump.  tests/spectral_loss_twin.py is the float64 restatement.
+ * pred, tgt: f32 contiguous [B][2][T][F], plane 0 real and plane 1 imaginary (F may be odd; 4-byte alignment only).  Parameters:
+ * compress c in (0, 1], mix lambda in [0, 1], eps > 0 (a power).  Everything is evaluated in f64 on the exactly converted f32 inputs,
+ * every operation rounded on its own.  Per bin, for pred (p) and tgt (t):
+ *   r  = re^2 + im^2 + eps          M = pow(r, c / 2)          g = pow(r, (c - 1) / 2)      (two pows: c = 1 gives g = 1 exactly)
+ *   e_r = p_r g_p - t_r g_t         e_i = p_i g_p - t_i g_t
+ *   mag term = (M_p - M_t)^2        complex term = e_r^2 + e_i^2
+ *   S_mag[b], S_cplx[b] = the sums over the T F bins of row b: a wave per (b, t) frame (lane l adds bins l, l + 64, ..., then a butterfly),
+ *   then the row's frames in index order
+ *   a_loss = ((1 - lambda) sum_b S_mag[b] + lambda sum_b S_cplx[b]) / (2 B T F)
+ * The denominator is the number of real elements: compress = 1, mix = 1 is the MSE a_loss of mse_pair (the mag term times an exact 0).
+ * The gradient with respect to pred, each element rounded once to f32:
+ *   s = e_r p_r + e_i p_i      q = (c - 1) g_p / r_p      k = (1 - lambda) (M_p - M_t) c M_p / r_p
+ *   d/dp_r = 2 grad_scale (k p_r + lambda (e_r g_p + q s p_r))      d/dp_i = 2 grad_scale (k p_i + lambda (e_i g_p + q s p_i))
+ * A bin that is zero on both sides has gradient 0; pred == tgt gives sums 0 and gradient 0 exactly; a non-finite input makes its row's
+ * sums non-finite and the gradient non-finite in the bins where this arithmetic says so.  No floating-point atomics: two runs give
+ * identical bytes, and a row of a batch has the bytes of a call of its own.
+ * maavss_spectral_loss: rows [B][2] f64 = {S_mag, S_cplx} per row; d_pred (nullable: the forward-only form writes no gradient) f32 of
+ * pred's shape.  ws: maavss_spectral_loss_ws_bytes(B, T) = round256(16 B T) bytes, 8-byte aligned [{mag, complex} per (b, t)]; 0 for
+ * invalid sizes.  Two launches.
+ * maavss_spectral_loss_pair: mse_pair with this audio term.  losses [3] f32 in mse_pair's positions: a_loss as above, v_loss and
+ * d_v (nullable) by mse_pair's own kernel and arithmetic (bit-identical to maavss_mse_pair's on the same operands),
+ * (a_loss + coeff v_loss) inv_num_seq; d_a (nullable) = the gradient above with grad_scale = inv_num_seq / (2 B T F); parts [2] f64 =
+ * sum_b S_mag / (2 B T F), sum_b S_cplx / (2 B T F).  ws: maavss_spectral_loss_pair_ws_bytes(B, T) bytes, 8-byte aligned. */
+int64_t maavss_spectral_loss_ws_bytes(int64_t B, int64_t T);
+int maavss_spectral_loss(const float* pred, const float* tgt, int64_t B, int64_t T, int64_t F, double compress, double mix, double eps,
+                         double grad_scale, float* d_pred, double* rows, void* ws, int64_t ws_bytes, void* stream);
+int64_t maavss_spectral_loss_pair_ws_bytes(int64_t B, int64_t T);
+int maavss_spectral_loss_pair(const float* a_pred, const float* a_tgt, int64_t B, int64_t T, int64_t F, double compress, double mix,
+                              double eps, const float* v_pred, const float* v_tgt, int64_t nv, float coeff, float inv_num_seq, float* d_a,
+                              float* d_v, float* losses, double* parts, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- EXTENSION: intelligibility scores (maavss_amd.stoi_metrics, Validator(intelligibility_sr=...)) -----------------------------
  * maavss_stoi: short-time objective intelligibility (STOI, Taal et al. 2011) and its extended form (ESTOI, Jensen & Taal 2016) of est
  * [rows][n] against ref [rows][n], f32 sampled at 10 kHz, per row.  Samples are widened to f64 on load and every operation from there on is

@@ -5,6 +5,7 @@
 //                one flat f32 parameter buffer (multi-tensor by construction: all parameters live in one buffer)
 #include "common.h"
 #include "bn_act.h"      // tanh_slope, sigmoid_slope
+#include "mse_term.h"    // MSE_BLK, mse_grad_scale, mse_term_mean: shared with spectral_loss.hip
 
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ out,
                                                       float* __restrict__ dz, int64_t n, int act) {
@@ -35,10 +36,7 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restric
 __global__ void mse_finalize_kernel(const float* __restrict__ pa, int na_blk, double na, const float* __restrict__ pv,
                                     int nv_blk, double nv, float coeff, float inv_num_seq, float* __restrict__ losses) {
   if (threadIdx.x != 0) return;
-  double sa = 0.0, sv = 0.0;
-  for (int i = 0; i < na_blk; ++i) sa += (double)pa[i];
-  for (int i = 0; i < nv_blk; ++i) sv += (double)pv[i];
-  const double la = sa / na, lv = sv / nv;
+  const double la = mse_term_mean(pa, na_blk, na), lv = mse_term_mean(pv, nv_blk, nv);
   losses[0] = (float)la;
   losses[1] = (float)lv;
   losses[2] = (float)((la + (double)coeff * lv) * (double)inv_num_seq);
@@ -134,17 +132,20 @@ extern "C" int maavss_act_bwd(const float* dout, const float* out, float* dz, in
   return MAAVSS_OK;
 }
 
-#define MSE_BLK 512
+int mse_term_launch(const float* pred, const float* target, int64_t n, float gscale, float* dpred, float* partials, hipStream_t st) {
+  const int g = (int)((n + 4095) / 4096 > MSE_BLK ? MSE_BLK : (n + 4095) / 4096);
+  hipLaunchKernelGGL(mse_partial_kernel, dim3(g), dim3(256), 0, st, pred, target, dpred, gscale, n, partials);
+  return g;
+}
+
 // ws: 2*MSE_BLK floats.  d_a / d_v nullable.  Gradients are those of losses[2].
 extern "C" int maavss_mse_pair(const float* a_pred, const float* a_tgt, int64_t na, const float* v_pred, const float* v_tgt,
                                int64_t nv, float coeff, float inv_num_seq, float* d_a, float* d_v, float* losses, float* ws,
                                void* stream) {
   MAAVSS_CHECK_ARG(a_pred && a_tgt && v_pred && v_tgt && losses && ws && na > 0 && nv > 0, "mse_pair: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  const int ga = (int)((na + 4095) / 4096 > MSE_BLK ? MSE_BLK : (na + 4095) / 4096);
-  const int gv = (int)((nv + 4095) / 4096 > MSE_BLK ? MSE_BLK : (nv + 4095) / 4096);
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(ga), dim3(256), 0, st, a_pred, a_tgt, d_a, 2.f * inv_num_seq / (float)na, na, ws);
-  hipLaunchKernelGGL(mse_partial_kernel, dim3(gv), dim3(256), 0, st, v_pred, v_tgt, d_v, 2.f * coeff * inv_num_seq / (float)nv, nv, ws + MSE_BLK);
+  const int ga = mse_term_launch(a_pred, a_tgt, na, mse_grad_scale(1.f, inv_num_seq, na), d_a, ws, st);
+  const int gv = mse_term_launch(v_pred, v_tgt, nv, mse_grad_scale(coeff, inv_num_seq, nv), d_v, ws + MSE_BLK, st);
   hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(64), 0, st, ws, ga, (double)na, ws + MSE_BLK, gv, (double)nv, coeff, inv_num_seq, losses);
   MAAVSS_LAUNCH_CHECK("mse_pair");
   return MAAVSS_OK;

@@ -523,6 +523,24 @@ def mse_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, num_seq=1, want_grads=True):
     return losses, d_a, d_v
 
 
+def spectral_loss_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, loss, num_seq=1, want_grads=True):
+    """mse_pair with the audio term replaced by `loss` (a maavss_amd.SpectralLoss) -> losses [3] in mse_pair's positions, d_a, d_v and
+    parts f64 [2] = the magnitude and the complex mean that losses[0] mixes.  losses[1] and d_v are mse_pair's, bit for bit."""
+    _f32(a_pred, a_tgt, v_pred, v_tgt)
+    assert a_pred.shape == a_tgt.shape and v_pred.shape == v_tgt.shape and a_pred.dim() == 4 and a_pred.shape[1] == 2
+    dev = a_pred.device
+    b, _, t, f = a_pred.shape
+    d_a = torch.empty_like(a_pred) if want_grads else None
+    d_v = torch.empty_like(v_pred) if want_grads else None
+    losses = torch.empty(3, device=dev, dtype=torch.float32)
+    parts = torch.empty(2, device=dev, dtype=torch.float64)
+    nbytes = int(query("maavss_spectral_loss_pair_ws_bytes", b, t))
+    ws = _lib.workspace(nbytes, dev)
+    call("maavss_spectral_loss_pair", ptr(a_pred), ptr(a_tgt), b, t, f, loss.compress, loss.mix, loss.eps, ptr(v_pred), ptr(v_tgt),
+         v_pred.numel(), float(coeff), 1.0 / num_seq, ptr(d_a), ptr(d_v), ptr(losses), ptr(parts), ptr(ws), nbytes, stream_ptr())
+    return losses, d_a, d_v, parts
+
+
 def adam_step(p, g, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
     _f32(p, g, m, v)
     call("maavss_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),

@@ -22,6 +22,7 @@ import torch
 
 from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr, workspace
 from .bss import BSS_COLUMNS, BSS_DB, BSS_MAX_FILTER, bss_eval_metrics
+from .spectral_loss import SpectralLoss
 from .stoi import stoi_metrics
 from .trainer import sliding_windows
 
@@ -127,6 +128,8 @@ _INTEL_LEN = 5 * len(_INTEL) * len(_GROUPS)
 # the third accumulator, only with bss_filter: the same five numbers for sdr_db, sir_db and sar_db of the same three groups
 _BSS_LEN = 5 * len(BSS_DB) * len(_GROUPS)
 _BSS0 = BSS_COLUMNS.index("sdr_db")
+# the fourth accumulator, only with audio_loss: [S_mag, S_cplx, elements] of the spectral loss over the model's audio outputs
+_SPEC_LEN = 3
 
 
 class Validator:
@@ -146,8 +149,12 @@ class Validator:
     The accumulator is one small f64 device tensor (`.acc`) of sums and counts only, so it is additive: the element-wise sum of the
     accumulators of several ranks is the accumulator of their data.  `add_*` enqueue kernels on the current stream and never wait."""
 
-    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10, intelligibility_sr=None, bss_filter=None):
-        """intelligibility_sr: the sample rate of the waves given to add_waves / add_recording; with it they also add STOI and ESTOI
+    def __init__(self, model, loss_coeff=0.001, num_seq=1, seg_len=256, lsd_floor=1e-10, audio_loss=None, intelligibility_sr=None,
+                 bss_filter=None):
+        """audio_loss: a maavss_amd.SpectralLoss; with it add_windows also runs its forward-only form on the model's audio output and
+        adds the two sums and the element count into a fourth accumulator (`.acc_spec`), and result() gains val_loss_spectral_mag,
+        val_loss_spectral_cplx, val_loss_spectral and val_objective.  None (the default): nothing of that is launched or reported.
+        intelligibility_sr: the sample rate of the waves given to add_waves / add_recording; with it they also add STOI and ESTOI
         (maavss_amd.stoi_metrics) of the estimate, of the noisy input and of estimate minus noisy per clip, into a second small
         accumulator (`.acc_intel`), and result() gains their keys.  None (the default): nothing of that is launched or reported.
         bss_filter: the length (1..512 taps) of the BSS-eval distortion filter; with it add_waves / add_recording also add sdr_db, sir_db
@@ -158,6 +165,8 @@ class Validator:
         if intelligibility_sr is not None and (isinstance(intelligibility_sr, bool) or not isinstance(intelligibility_sr, int)
                                                or intelligibility_sr < 1):
             raise ValueError(f"intelligibility_sr must be None or a positive integer (samples per second), got {intelligibility_sr!r}")
+        if audio_loss is not None and not isinstance(audio_loss, SpectralLoss):
+            raise ValueError(f"audio_loss must be None or a maavss_amd.SpectralLoss, got {audio_loss!r}")
         if int(num_seq) < 1:
             raise ValueError("num_seq must be >= 1")
         if int(seg_len) < 1:
@@ -168,9 +177,11 @@ class Validator:
         self.seg_len, self.lsd_floor = int(seg_len), float(lsd_floor)
         self.intelligibility_sr = intelligibility_sr
         self.bss_filter = bss_filter
+        self.audio_loss = audio_loss
         self.acc = None
         self.acc_intel = None        # with intelligibility_sr: the tail of the allocation `acc` heads, so that result() makes one copy
         self.acc_bss = None          # with bss_filter: the tail after that
+        self.acc_spec = None         # with audio_loss: the last tail
         self._buf = None
         self.best = None
 
@@ -187,11 +198,14 @@ class Validator:
             if extra:
                 self.acc_intel = self._buf[_ACC_LEN:_ACC_LEN + extra]
             if self.bss_filter is not None:
-                self.acc_bss = self._buf[_ACC_LEN + extra:]
+                self.acc_bss = self._buf[_ACC_LEN + extra:_ACC_LEN + extra + _BSS_LEN]
+            if self.audio_loss is not None:
+                self.acc_spec = self._buf[self._buf_len() - _SPEC_LEN:]
         return self.acc
 
     def _buf_len(self):
-        return _ACC_LEN + (0 if self.intelligibility_sr is None else _INTEL_LEN) + (0 if self.bss_filter is None else _BSS_LEN)
+        return (_ACC_LEN + (0 if self.intelligibility_sr is None else _INTEL_LEN) + (0 if self.bss_filter is None else _BSS_LEN)
+                + (0 if self.audio_loss is None else _SPEC_LEN))
 
     def _slot(self, kind, group=None):
         if group is None:
@@ -222,6 +236,11 @@ class Validator:
         call("maavss_metric_add_sum", ptr(spec[:, 1]), b, 2, 1.0, ptr(self._slot("lsd")), st)
         attn = sqerr_rows(v, y_v)
         call("maavss_metric_add_sum", ptr(attn), b, 1, float(v.numel() // b), ptr(self._slot("attn")), st)
+        if self.audio_loss is not None:
+            rows = self.audio_loss(a, y_a)["rows"]
+            # add_sum adds a sum to acc[0] and n * weight to acc[1]: S_cplx and the elements into [1:3], then S_mag into [0] (and 0 into [1])
+            call("maavss_metric_add_sum", ptr(rows[:, 1]), b, 2, float(a.numel() // b), ptr(self.acc_spec[1:]), st)
+            call("maavss_metric_add_sum", ptr(rows), b, 2, 0.0, ptr(self.acc_spec), st)
 
     def add_clips(self, x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame):
         """One batch of clips, cut into the `num_seq` windows TrainStep.sliding_window_step trains on (the same slicing code)."""
@@ -294,7 +313,10 @@ class Validator:
         their _n_finite / _n_nan counts: a clip without a 384 ms segment, or with a non-finite sample, counts as NaN.
         With bss_filter also sdr_db, sir_db, sar_db, their noisy_ and _improvement forms (always all nine) and the four counts of each:
         a clip with a status (a non-finite sample, a silent target, a pivot that is not positive) counts as NaN, one without another
-        live source has sir_db = +inf."""
+        live source has sir_db = +inf.
+        With audio_loss also val_loss_spectral_mag and val_loss_spectral_cplx (each sum over the total elements), val_loss_spectral =
+        (1 - mix) mag + mix cplx and val_objective = val_loss_spectral + loss_coeff * val_loss_attn: what TrainStep(audio_loss=...)
+        minimises, on the held-out data."""
         nan = float("nan")
         if self._buf is None:
             h = [0.0] * self._buf_len()
@@ -335,12 +357,18 @@ class Validator:
                     key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
                     out[key] = ratio(s, nf)
                     out.update({f"{key}_n_finite": int(nf), f"{key}_n_posinf": int(npos), f"{key}_n_neginf": int(nneg), f"{key}_n_nan": int(nnan)})
+        if self.audio_loss is not None:
+            s_mag, s_cplx, n = h[o:o + _SPEC_LEN]
+            out["val_loss_spectral_mag"], out["val_loss_spectral_cplx"] = ratio(s_mag, n), ratio(s_cplx, n)
+            out["val_loss_spectral"] = ratio((1.0 - self.audio_loss.mix) * s_mag + self.audio_loss.mix * s_cplx, n)
+            out["val_objective"] = out["val_loss_spectral"] + self.loss_coeff * out["val_loss_attn"]
         return out
 
-    def improved(self, result):
-        """True when result["val_loss"] is lower than every one seen before (and keeps it in `.best`): the reference's "save on
-        improvement" (train_av_net.py:174-181).  A NaN loss never improves."""
-        loss = float(result["val_loss"])
+    def improved(self, result, key="val_loss"):
+        """True when result[key] is lower than every one seen before (and keeps it in `.best`): the reference's "save on
+        improvement" (train_av_net.py:174-181); key="val_objective" follows the loss a TrainStep(audio_loss=...) trains on.  A NaN
+        loss never improves."""
+        loss = float(result[key])
         if loss == loss and (self.best is None or loss < self.best):
             self.best = loss
             return True

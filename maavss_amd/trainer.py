@@ -22,6 +22,7 @@ which reproduces the single-device reference on the concatenated batch -- docume
 import torch
 
 from . import ops
+from .spectral_loss import SpectralLoss
 
 _FUSION_PREFIXES = ("lstm.", "fc1.", "fc2.", "a_fc1.", "v_fc1.")
 
@@ -377,8 +378,12 @@ class TrainStep:
     """One optimizer step of the fusion network, autograd-free (see module docstring)."""
 
     def __init__(self, model, lr=1e-5, loss_coeff=0.001, num_seq=1, betas=(0.9, 0.999), eps=1e-8,
-                 process_group=None, sync_bn=False, grad_wire_dtype=None, max_grad_norm=None):
-        """`max_grad_norm`: FusedAdam's gradient-norm clipping.  It runs once per optimizer step, in the `last` window after the
+                 process_group=None, sync_bn=False, grad_wire_dtype=None, max_grad_norm=None, audio_loss=None):
+        """`audio_loss`: None trains on the reference's MSE of the STFT planes (ops.mse_pair); a maavss_amd.SpectralLoss replaces that
+        term by the power-law compressed spectral loss (ops.spectral_loss_pair): `losses` keeps its three positions (losses[0] is the
+        new audio loss, losses[1] the attention MSE by mse_pair's own kernel) and `loss_parts` holds the magnitude and the complex
+        mean (device f64 [2]) that losses[0] mixes.
+        `max_grad_norm`: FusedAdam's gradient-norm clipping.  It runs once per optimizer step, in the `last` window after the
         all-reduce has finished, on the accumulated, summed gradient times 1 / world -- the norm of the AVERAGED gradient, as DDP
         followed by clip_grad_norm_ gives; every rank computes it from identical bytes, so there is no extra collective."""
         self.model = model
@@ -390,7 +395,11 @@ class TrainStep:
         self.sync.broadcast([self.flat.params] + [b for _, b in model.named_buffers()])
         if sync_bn and self.sync.enabled:
             model.set_bn_sync(self.sync.sum_)
+        if audio_loss is not None and not isinstance(audio_loss, SpectralLoss):
+            raise ValueError(f"audio_loss must be None or a maavss_amd.SpectralLoss, got {audio_loss!r}")
+        self.audio_loss = audio_loss
         self.losses = None
+        self.loss_parts = None
 
     def __call__(self, x_a, x_v, y_a, y_v, optimizer_step=True, accumulate=False, last=True):
         """One window: forward, loss / num_seq, backward.  `accumulate` adds into the flat gradient buffer instead of
@@ -403,7 +412,11 @@ class TrainStep:
             self.flat.touched.clear()
         (a, v, fused), sv = m._engine_forward(x_a, x_v, train=True)
         self.outputs = (a, v, fused)
-        self.losses, d_a, d_v = ops.mse_pair(a, y_a.contiguous(), v, y_v.contiguous(), self.loss_coeff, self.num_seq)
+        if self.audio_loss is None:
+            self.losses, d_a, d_v = ops.mse_pair(a, y_a.contiguous(), v, y_v.contiguous(), self.loss_coeff, self.num_seq)
+        else:
+            self.losses, d_a, d_v, self.loss_parts = ops.spectral_loss_pair(a, y_a.contiguous(), v, y_v.contiguous(), self.loss_coeff,
+                                                                            self.audio_loss, self.num_seq)
         if last:
             self.sync.begin(n for n in m._param_names if need.get(n, False))
         out = m._engine_backward(sv, d_a, d_v, None, need, grads=self.flat.grad_views, accumulate=accumulate,
