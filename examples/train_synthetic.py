@@ -15,6 +15,9 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
     python examples/train_synthetic.py --bank 8 [--bank_storage u16]          # the ViT once per recording: maps and audio of 8 recordings in
                                                                               # HBM (ClipBank), every batch cut from them by clip index
+    python examples/train_synthetic.py --bank 8 --select [--val 2]            # every recording gets a silent and a frozen stretch; the bank's
+                                                                              # activity pass finds them and maavss_amd.ClipSampler draws the
+                                                                              # epochs from the clips that are left (held-out recordings: --val)
     python examples/train_synthetic.py --figures 2 [--figures-dir figures]    # every 2 steps the reference's callback images as PNGs
                                                                               # (maavss_amd.CallbackFigures: train_avse_frames.py:191-215)
     python examples/train_synthetic.py --audio_loss compressed [--compress 0.3 --loss_mix 0.3]    # the power-law compressed spectral loss
@@ -64,6 +67,9 @@ def main():
                     help="bank R synthetic recordings of 4 clips once (ViT + audio, maavss_amd.ClipBank: the reference's attn_frames_path / "
                          "use_audio_memmap), then draw every batch by clip index from a seeded permutation: no ViT in the step")
     ap.add_argument("--bank_storage", choices=("f32", "u16"), default="f32", help="with --bank: 4 or 2 bytes per map value")
+    ap.add_argument("--select", action="store_true",
+                    help="with --bank: silence the first clip of every recording and freeze the frames of its last one, reject such clips by the "
+                         "bank's activity statistics and iterate maavss_amd.ClipSampler's epochs instead of a hand-drawn permutation")
     ap.add_argument("--figures", type=int, default=0, metavar="N",
                     help="every N steps (the reference's cb_freq), run the step with collect=True and make the callback's images on the "
                          "device (maavss_amd.CallbackFigures), then write them as PNGs")
@@ -75,6 +81,8 @@ def main():
                     help="with --audio_loss compressed: the weight of the complex term, in [0, 1]; the magnitude term gets 1 - L")
     ap.add_argument("--figures-dir", default="figures", metavar="D", help="with --figures: where the PNGs go")
     a = ap.parse_args()
+    if a.select and not a.bank:
+        ap.error("--select chooses among the clips of a bank: it goes with --bank")
     if a.bank and (a.raw_video or a.raw_audio or a.overfit):
         ap.error("--bank holds transformed frames' maps and 16 kHz audio: it does not go with --raw_video, --raw_audio or --overfit")
     dev = torch.device("cuda:0")
@@ -140,11 +148,15 @@ def main():
         per_rec, frame_hop = 4, max(1, t_total // 2)
         n_f = (per_rec - 1) * frame_hop + t_total
         n_s = (per_rec - 1) * frame_hop * 16000 // 30 + 1 + length
-        n_rec = a.bank + (-(-b // per_rec) if a.val else 0)          # --val: the last recordings are held out
+        keep = per_rec - 2 if a.select else per_rec                  # --select: two clips of every recording are made to be rejected
+        n_rec = a.bank + (-(-b // keep) if a.val else 0)             # --val: the last recordings are held out
         bank = maavss_amd.ClipBank(w, t_total, frame_hop, hpf, hop, capacity_frames=n_rec * n_f, capacity_samples=n_rec * n_s,
                                    storage=a.bank_storage, device=dev)
         for _ in range(n_rec):
             frames, audio = batch(1, n_f, n_s)
+            if a.select:
+                audio[0, :length] = 0.0                                  # clip 0: digital silence
+                frames[-t_total:] = frames[-1].clone()                   # the last clip: one frame, repeated
             bank.add_recording(audio[0], frames=frames, video_attention=extractor)
         n_train = a.bank * per_rec
         if n_train < b:
@@ -153,16 +165,36 @@ def main():
               f"({a.bank_storage}), {bank.audio.numel() * 4 / 1e6:.2f} MB of audio", flush=True)
         pipe = maavss_amd.ClipPipeline(None, stft, clip_frames=t_total, bank=bank, mixer=mixer)
         g_order, order = torch.Generator().manual_seed(0), []
+        if a.select:
+            # one pass over the bank on the device (ClipBank.activity), the thresholds there too, one copy of a byte per clip back
+            limits = dict(min_rms_db=-50.0, min_motion=1e-4)
+            sampler = maavss_amd.ClipSampler(bank, b, recordings=range(a.bank), seed=0, **limits)
+            print(f"select: {sampler.accepted.numel()} of {sampler.n_considered} training clips accepted, {len(sampler)} steps an epoch; rejected "
+                  + ", ".join(f"{k} {v}" for k, v in sampler.rejected.items() if v), flush=True)
 
-        def submit(seed):
-            while len(order) < b:                                        # the next epoch's permutation of the training clips
-                order.extend(torch.randperm(n_train, generator=g_order).tolist())
-            pipe.submit_clips([order.pop(0) for _ in range(b)], seed=seed)
+            def batches():
+                e = 0
+                while True:
+                    yield from sampler.epoch(e)
+                    e += 1
+            epochs = batches()
+
+            def submit(seed):
+                pipe.submit_clips(next(epochs), seed=seed)
+        else:
+            def submit(seed):
+                while len(order) < b:                                    # the next epoch's permutation of the training clips
+                    order.extend(torch.randperm(n_train, generator=g_order).tolist())
+                pipe.submit_clips([order.pop(0) for _ in range(b)], seed=seed)
 
     held_out = validator = val_dir = None
     if a.val:
         # one held-out batch from a generator of its own (the training stream's draws stay what they are without --val), extracted once
-        if a.bank:
+        if a.select:
+            held = maavss_amd.ClipSampler(bank, b, recordings=range(a.bank, n_rec), shuffle=False, **limits)      # the split by file
+            print(f"select: {held.accepted.numel()} of {held.n_considered} held-out clips accepted", flush=True)
+            pipe.submit_clips(next(held.epoch(0)), seed=12345)
+        elif a.bank:
             pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345)
         else:
             g_train, g = g, torch.Generator().manual_seed(12345)

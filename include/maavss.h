@@ -690,6 +690,62 @@ int maavss_bank_attn_clips(const void* maps, int storage, const int32_t* clip_st
 int maavss_bank_audio_clips(const float* bank, int64_t n_samples, const int64_t* clip_start, int64_t n_clips, int64_t L, float* out,
                             int64_t ld_out, void* stream);
 
+/* ---- EXTENSION: per-clip activity statistics of the clip bank (maavss_amd.ClipBank.activity, maavss_amd.ClipSampler) ------------
+ * Which clips of a bank are silent, still or cut (the reference's to_do.txt: "audio thresholding", "video reject"), from one read of
+ * the bank.  T = clip_frames, P = frame_elems, hop, J = hops_per_frame * T segments of hop samples that tile a clip of n = J * hop
+ * samples exactly; clip b starts at bank frame v = clip_frame[b] and bank sample s = clip_sample[b] and belongs to recording
+ * r = clip_rec[b].  Every sum is f64 over the exactly converted f32 data (a square of an f32 is exact in f64), in the ONE order
+ * stated here; no atomics; two runs give identical bytes, and a clip's row does not depend on which other clips or recordings the
+ * tables hold.  tests/select_twin.py restates all of it.  The library does not allocate and does not synchronise.  Every table exists
+ * twice: on the device for the kernels, which clamp what they read from it, and in host memory (host_*), which the entry point checks
+ * entry by entry before any launch.  Additive symbols (nothing existing changed meaning).
+ *
+ * Recording level.  rec_tab int64 [3][n_rec]: first bank sample, samples N_r, first partial slot (the running count of
+ * maavss_bank_level_chunks(N_q), q < r) of each recording.  A chunk is 16384 consecutive samples from the recording's first (the last
+ * one shorter).  Chunk partial: "thread" t of 256 adds the squares of the chunk's samples t, t + 256, ... in index order, a NON-FINITE
+ * sample counting as 0 (so that a bad sample disturbs only the clips that hold it); the 64 sums of each of the four "waves" (threads
+ * 64 w .. 64 w + 63) go through the butterfly v[l] += v[l ^ o], o = 32, 16, 8, 4, 2, 1; the four results as (w0 + w1) + (w2 + w3).
+ * level[r] = the recording's partials added in index order, from 0.  partials: n_partials doubles of workspace.  Two launches.
+ * At most 65535 chunks (1.07e9 samples) per recording. */
+int64_t maavss_bank_level_chunks(int64_t samples);
+int maavss_bank_recording_level(const float* audio, int64_t n_samples, const int64_t* rec_tab, const int64_t* host_rec_tab,
+                                int64_t n_rec, double* partials, int64_t n_partials, double* level, void* stream);
+/* D [n_frames - 1] f64: D[f] = (sum_e |m[f+1][e] - m[f][e]|) / P over the stored maps [n_frames][P] as the bank's batches read them
+ * (storage 0: f32; 1: the correctly rounded f32 quotient q / 65535), for every pair of consecutive bank frames, once each (the pair
+ * that straddles two recordings too: no clip uses it).  Difference and absolute value in f64; "lane" l of 64 adds the terms
+ * e = l, l + 64, ... in index order, the 64 sums through the butterfly above, then one division.  One launch, one wave per pair. */
+int maavss_bank_frame_motion(const void* maps, int storage, int64_t n_frames, int64_t frame_elems, double* D, void* stream);
+/* Per clip b (one workgroup each), all outputs [n_clips]:
+ *   E_j       segment j = samples s + j hop .. s + (j + 1) hop - 1: lane l adds the squares of the segment's samples l, l + 64, ... in
+ *             index order (non-finite samples included: IEEE decides), the 64 sums through the butterfly above
+ *   energy    E_0 + E_1 + ... + E_{J-1} added in index order, from 0
+ *   rms_db    10 * log10(energy / n): -inf for silence
+ *   rel_db    10 * log10((energy / n) / (level[r] / N_r)): NaN in a recording whose level is 0
+ *   peak      max |x_i| in f32 over the clip's samples that are not NaN (fmaxf from 0), exact
+ *   n_bad     the number of samples that are inf or NaN
+ *   n_active  the number of segments with   E_j / (double)hop >= (level[r] / (double)N_r) * floor_factor   (three f64 operations and
+ *             one comparison, as written; a NaN on either side is not active; in a recording whose level is 0 every segment is),
+ *             floor_factor = 10^(-range_db / 10) formed by the caller, in [0, 1]
+ *   motion_mean  (D[v] + D[v+1] + ... + D[v+T-2]) / (T - 1), added in index order from 0;  motion_peak  the largest of those D, from 0,
+ *             by `d > m` (a NaN is passed over); both 0 when T = 1 (D may then be null).  Only pairs inside the clip's frames are read.
+ * level, D: what the two entry points above wrote.  J is limited to maavss_bank_max_segments() = 2048 (the E_j stay in LDS): a larger
+ * J, a clip outside the bank or a recording number outside [0, n_rec) in the host tables is refused before any launch.  One launch. */
+int maavss_bank_max_segments(void);
+int maavss_bank_clip_activity(const float* audio, int64_t n_samples, const double* D, int64_t n_frames, const double* level,
+                              const int64_t* rec_tab, int64_t n_rec, const int64_t* clip_sample, const int32_t* clip_frame,
+                              const int32_t* clip_rec, const int64_t* host_clip_sample, const int32_t* host_clip_frame,
+                              const int32_t* host_clip_rec, int64_t n_clips, int clip_frames, int hops_per_frame, int hop,
+                              double floor_factor, double* energy, double* rms_db, double* rel_db, double* motion_mean,
+                              double* motion_peak, float* peak, int32_t* n_bad, int32_t* n_active, void* stream);
+/* reasons uint8 [n_clips]: bit 0 too quiet (rms_db < min_rms_db), 1 too quiet for its recording (rel_db < min_rel_db), 2 too few active
+ * segments ((double)n_active < min_active; the caller passes min_active_fraction * J), 3 static (motion_mean < min_motion), 4 scene cut
+ * (motion_peak > max_motion_peak), 5 clipped (peak >= max_peak, in f32), 6 non-finite (n_bad > 0); and-ed with `enabled` (bit k: reason
+ * k is tested; the threshold of a reason that is not is ignored).  A comparison with a NaN statistic is false.  One launch. */
+int maavss_bank_clip_select(const double* rms_db, const double* rel_db, const int32_t* n_active, const double* motion_mean,
+                            const double* motion_peak, const float* peak, const int32_t* n_bad, int64_t n_clips, int enabled,
+                            double min_rms_db, double min_rel_db, double min_active, double min_motion, double max_motion_peak,
+                            float max_peak, void* reasons, void* stream);
+
 /* ---- the training callback's images (maavss_amd.figures; train_avse_frames.py:191-215) ----------------------------------------------
  * RGBA bytes made on the device, defined pixel for pixel by matplotlib's colour mapping; tests/figures_twin.py restates every definition
  * below in float64.  No entry point allocates, synchronises or uses an atomic; two runs give the same bytes.  Additive symbols (nothing

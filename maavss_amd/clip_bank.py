@@ -21,9 +21,13 @@ value * (1 / m)).  Against f32 storage the maps differ by at most 1/131070 (half
 and the quotient) before the clip normalisation, in half the bytes.
 A clip never reads a map or a sample of a neighbouring recording, with attn_diff too (clip frame 0 is 0 * (1 / m)).
 tests/bank_twin.py restates the pack and the index on the host.
+
+`activity()` is one pass over the bank that says which clips are silent, still or cut (csrc/clip_select.hip; tests/select_twin.py);
+maavss_amd.ClipSampler turns it into the clips an epoch trains on.
 """
 from bisect import bisect_right
 from fractions import Fraction
+from itertools import accumulate
 
 import torch
 
@@ -86,6 +90,7 @@ class ClipBank:
         self.recordings = []                          # per recording (first frame, first sample, frames, samples, clips)
         self._clip_ends = []                          # running total of clips after each recording
         self._tables = None                           # the same as CPU tensors, for batch()
+        self._activity = None                         # (range_db, activity()'s result), until the next add_recording
 
     # ---- the clip index: pure host arithmetic ---------------------------------------------------------
     def __len__(self):
@@ -112,7 +117,7 @@ class ClipBank:
         self._clip_ends.append(len(self) + n_clips)
         self.n_frames += n_frames
         self.n_samples += n_samples
-        self._tables = None
+        self._tables = self._activity = None
 
     def _check_recording(self, audio, frames, maps, video_attention):
         """Every refusal of add_recording, on shapes and the bank's fill alone -> (clips, frames used, samples used)."""
@@ -263,6 +268,67 @@ class ClipBank:
              int(bool(attn_diff)), ptr(rcp), ptr(attn), st)
         call("maavss_bank_audio_clips", ptr(self.audio), self.n_samples, ptr(staged), b, n, ptr(audio), audio.stride(0) if b > 1 else n, st)
         return attn, audio
+
+    # ---- which clips are worth a step ---------------------------------------------------------------------
+    def clip_recordings(self):
+        """The recording every clip belongs to: CPU int32 [len(bank)], pure host arithmetic."""
+        ends = torch.tensor(self._clip_ends, dtype=torch.int64)
+        return torch.bucketize(torch.arange(len(self), dtype=torch.int64), ends, right=True).to(torch.int32)
+
+    def activity(self, range_db=40.0):
+        """Per-clip activity statistics of every banked clip, computed on the device next to the data (csrc/clip_select.hip; the
+        definitions and the order of every sum are in include/maavss.h, restated by tests/select_twin.py) -> a dict of device tensors
+        of length len(bank):
+          f64  energy (sum of squares), rms_db = 10 log10(energy / clip_samples) (-inf for silence), rel_db (the same against the mean
+               power of the clip's recording), motion_mean and motion_peak (mean / largest mean absolute difference of consecutive
+               stored maps inside the clip; 0 for clips of one frame)
+          f32  peak (max |x|)
+          i32  n_bad (inf or NaN samples), n_active (segments of `hop` samples whose mean power is at least the recording's mean power
+               less range_db decibels -- the dynamic-range rule STOI uses for silent frames), recording
+        The clip tables are uploaded once from pinned memory and four launches follow on the current stream: no synchronisation.  The
+        result is cached until the next add_recording (save / load do not store it: the pass is cheaper than a format change).
+        `ClipSampler` turns the table into the clips to train on."""
+        if not isinstance(range_db, (int, float)) or isinstance(range_db, bool) or not 0.0 <= range_db <= 3000.0:
+            raise ValueError(f"range_db must be a number in [0, 3000], got {range_db!r}")
+        range_db = float(range_db)
+        if self._activity is not None and self._activity[0] == range_db:
+            return self._activity[1]
+        c, r = len(self), len(self.recordings)
+        if c == 0:
+            raise ValueError("the bank holds no clip")
+        j = self.hops_per_frame * self.clip_frames
+        if j > _lib.query("maavss_bank_max_segments"):
+            raise ValueError(f"hops_per_frame * clip_frames = {j} segments per clip, the activity kernel holds {_lib.query('maavss_bank_max_segments')}")
+        _lib.require_cuda(self.maps, self.audio)
+        frame_start, sample_start = self.check_indices(torch.arange(c, dtype=torch.int64))
+        rec = self.clip_recordings()
+        chunks = [_lib.query("maavss_bank_level_chunks", q[3]) for q in self.recordings]
+        first = [0] + list(accumulate(chunks))[:-1]          # a recording's first chunk partial: the running chunk count
+        rec_tab = torch.tensor([[q[1] for q in self.recordings], [q[3] for q in self.recordings], first], dtype=torch.int64)
+        # one copy through pinned memory, as cut() stages its tables: the int64 tables first (8-byte aligned), then the int32 ones
+        host = torch.cat([sample_start.view(torch.int32), rec_tab.reshape(-1).view(torch.int32), frame_start, rec]).pin_memory()
+        staged = torch.empty(host.numel(), device=self.device, dtype=torch.int32)
+        staged.copy_(host, non_blocking=True)
+        o_rec, o_frame, o_clip_rec = 2 * c, 2 * c + 6 * r, 3 * c + 6 * r
+        f64 = {k: torch.empty(c, device=self.device, dtype=torch.float64) for k in ("energy", "rms_db", "rel_db", "motion_mean", "motion_peak")}
+        peak = torch.empty(c, device=self.device, dtype=torch.float32)
+        n_bad, n_active = (torch.empty(c, device=self.device, dtype=torch.int32) for _ in range(2))
+        partials = torch.empty(sum(chunks), device=self.device, dtype=torch.float64)
+        level = torch.empty(r, device=self.device, dtype=torch.float64)
+        st = stream_ptr()
+        call("maavss_bank_recording_level", ptr(self.audio), self.n_samples, ptr(staged[o_rec:]), ptr(host[o_rec:]), r, ptr(partials),
+             partials.numel(), ptr(level), st)
+        motion = None
+        if self.clip_frames > 1:
+            motion = torch.empty(self.n_frames - 1, device=self.device, dtype=torch.float64)
+            call("maavss_bank_frame_motion", ptr(self.maps), _STORAGE[self.storage][0], self.n_frames, self.frame_elems, ptr(motion), st)
+        call("maavss_bank_clip_activity", ptr(self.audio), self.n_samples, ptr(motion), self.n_frames, ptr(level), ptr(staged[o_rec:]), r,
+             ptr(staged), ptr(staged[o_frame:]), ptr(staged[o_clip_rec:]), ptr(host), ptr(host[o_frame:]), ptr(host[o_clip_rec:]), c,
+             self.clip_frames, self.hops_per_frame, self.hop, 10.0 ** (-range_db / 10.0), ptr(f64["energy"]), ptr(f64["rms_db"]),
+             ptr(f64["rel_db"]), ptr(f64["motion_mean"]), ptr(f64["motion_peak"]), ptr(peak), ptr(n_bad), ptr(n_active), st)
+        out = dict(f64, peak=peak, n_bad=n_bad, n_active=n_active, recording=staged[o_clip_rec:o_clip_rec + c])
+        self._activity = (range_db, out)
+        return out
 
     # ---- one file -----------------------------------------------------------------------------------------
     def save(self, path):

@@ -22,13 +22,9 @@
 //                     element stores otherwise and in a row's last L % 4 samples.  Offsets are 64-bit.  Reads and writes B * L * 4 B.
 // One body serves both storages: the kernels are templates over the stored type and differ in bank_load alone.
 #include "common.h"
+#include "bank_load.h"      // bank_load (both storages), bank_clamp
 
 namespace {
-
-__device__ __forceinline__ float bank_load(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float bank_load(const uint16_t* p, int64_t i) { return __fdiv_rn((float)p[i], 65535.f); }
-
-__device__ __forceinline__ int64_t bank_clamp(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(256) void bank_pack_u16_kernel(const float* __restrict__ maps, uint16_t* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
