@@ -22,6 +22,10 @@ stream (ClipPipeline).
                                                                               # (maavss_amd.CallbackFigures: train_avse_frames.py:191-215)
     python examples/train_synthetic.py --audio_loss compressed [--compress 0.3 --loss_mix 0.3]    # the power-law compressed spectral loss
                                                                               # as the audio term (goes with --val, --mix and --overfit)
+    python examples/train_synthetic.py --weight_decay 0.01 --ema 0.99 --skip_nonfinite --warmup 3 --schedule cosine [--val 2]
+                                                                              # AdamW decay, averaged weights, the non-finite skip and a
+                                                                              # warm-up + cosine rate (FusedAdam / maavss_amd.LRSchedule);
+                                                                              # with --val both the raw and the averaged val_loss
 """
 import argparse
 import os
@@ -80,6 +84,14 @@ def main():
     ap.add_argument("--loss_mix", type=float, default=0.3, metavar="L",
                     help="with --audio_loss compressed: the weight of the complex term, in [0, 1]; the magnitude term gets 1 - L")
     ap.add_argument("--figures-dir", default="figures", metavar="D", help="with --figures: where the PNGs go")
+    ap.add_argument("--weight_decay", type=float, default=0.0, metavar="W", help="AdamW's decoupled decay on the tensors with two or more dimensions")
+    ap.add_argument("--ema", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights with this decay (warmed up); with --val the averaged weights are "
+                         "validated too, inside step.ema_weights()")
+    ap.add_argument("--skip_nonfinite", action="store_true", help="skip an optimizer step whose gradient norm is NaN or infinite, on the device")
+    ap.add_argument("--warmup", type=int, default=0, metavar="N", help="linear warm-up of the learning rate over N steps (maavss_amd.LRSchedule)")
+    ap.add_argument("--schedule", choices=("constant", "linear", "cosine"), default="constant",
+                    help="the rate after the warm-up: constant, or a linear / cosine decay to 0 at --steps")
     a = ap.parse_args()
     if a.select and not a.bank:
         ap.error("--select chooses among the clips of a bank: it goes with --bank")
@@ -95,7 +107,13 @@ def main():
     stft = maavss_amd.STFT(a.fft_len, hop, noise_std=0.1, device=dev)
     model = maavss_amd.AV_Fusion_Model_Frames([b, 2, hpf * nf, n_bins], [b, 1, nf, w, w], hpf, precise=a.precise).to(dev).train()
     audio_loss = maavss_amd.SpectralLoss(a.compress, a.loss_mix) if a.audio_loss == "compressed" else None
-    step = maavss_amd.TrainStep(model, lr=a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip, audio_loss=audio_loss)
+    schedule = None
+    if a.warmup or a.schedule != "constant":
+        schedule = maavss_amd.LRSchedule(a.lr, warmup_steps=a.warmup, total_steps=None if a.schedule == "constant" else max(a.steps, a.warmup + 1),
+                                         kind=a.schedule)
+    step = maavss_amd.TrainStep(model, lr=schedule if schedule is not None else a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip,
+                                audio_loss=audio_loss, weight_decay=a.weight_decay, ema_decay=a.ema, ema_warmup=a.ema is not None,
+                                skip_nonfinite=a.skip_nonfinite)
     watch = maavss_amd.ModelWatch(step, log_freq=a.watch) if a.watch else None
     figures = maavss_amd.CallbackFigures(stft) if a.figures else None
     transform = None
@@ -235,18 +253,30 @@ def main():
         if i % a.log_every == 0 or i == a.steps - 1:
             clip = "" if a.clip is None else f"  |g| {step.opt.grad_norm.item():.4g}  scale {step.opt.clip_scale.item():.4g}"
             parts = "" if audio_loss is None else "  (magnitude {:.5f}, complex {:.5f})".format(*step.loss_parts.tolist())
-            print(f"step {i}: a_loss {losses[0].item():.5f}{parts}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}", flush=True)
+            rate = "" if schedule is None else f"  lr {step.opt.lr:.3g}"
+            skips = "" if not a.skip_nonfinite else f"  skipped {step.opt.skipped_steps.item()}"
+            print(f"step {i}: a_loss {losses[0].item():.5f}{parts}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}{rate}{skips}",
+                  flush=True)
         if validator is not None and (i + 1) % a.val == 0:
             attn_v, x_v_stft, y_v_stft = held_out
             model.eval()
             validator.reset()
             validator.add_clips(x_v_stft, y_v_stft, attn_v, attn_v, nf, hpf)
             res = validator.result()
+            if a.ema is not None:
+                # the same held-out batch through the averaged weights (BatchNorm keeps its live running statistics)
+                with step.ema_weights():
+                    validator.reset()
+                    validator.add_clips(x_v_stft, y_v_stft, attn_v, attn_v, nf, hpf)
+                    res_ema = validator.result()
+                print(f"step {i}: val_loss raw {res['val_loss']:.5f}  averaged {res_ema['val_loss']:.5f} ({step.opt.ema_updates} updates)", flush=True)
             model.train()
             print(f"step {i}: validation {res}", flush=True)
             key = "val_loss" if audio_loss is None else "val_objective"          # the loss the step trains on
             if validator.improved(res, key=key):
-                maavss_amd.save_checkpoint(model.state_dict(), step.opt.state_dict(), i, res[key], "synthetic-best", val_dir.name)
+                maavss_amd.save_checkpoint(model.state_dict(), step.opt.state_dict(), i, res[key], "synthetic-best", val_dir.name,
+                                           ema_dict=step.opt.ema_state_dict() if a.ema is not None else None,
+                                           schedule_dict=schedule.state_dict() if schedule is not None else None)
                 print(f"step {i}: {key} {res[key]:.5f} improved: checkpoint saved", flush=True)
         if logs is not None:
             # with wandb: wandb.log({k: wandb.Histogram(np_histogram=v) for k, v in logs.items() if not k.startswith("nonfinite/")})
@@ -263,6 +293,7 @@ def main():
         fresh = maavss_amd.AV_Fusion_Model_Frames([b, 2, hpf * nf, n_bins], [b, 1, nf, w, w], hpf).to(dev)
         opt = maavss_amd.FusedAdam(fresh, lr=a.lr)
         maavss_amd.load_checkpoint(fresh, opt, cp_dir, auto=True, load_opt=True)
+        assert opt.weight_decay == a.weight_decay
         same = all(torch.equal(p, q) for p, q in zip(model.state_dict().values(), fresh.state_dict().values()))
         print("checkpoint round trip:", "ok" if same else "MISMATCH")
         if not same:

@@ -300,6 +300,39 @@ int maavss_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 int maavss_adam_step_dscale(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                             float eps, int64_t step, const float* grad_scale_dev, void* stream);
 
+/* ---- EXTENSION: AdamW decay, weight average and non-finite step skip in the optimizer kernel (maavss_amd.FusedAdam) --------------
+ * NOT in the reference, whose optimizer is torch.optim.Adam at one fixed rate (train_avse_frames.py:92): decoupled weight decay per
+ * tensor (torch.optim.AdamW's update), an exponential moving average of the weights (lerp(ema, p, 1 - d)) and the skip of a step whose
+ * gradient norm is not finite, in one launch per contiguous run of stepped parameters.  Added without a version bump; maavss_adam_step
+ * and maavss_adam_step_dscale are unchanged (they are compiled with contraction and are not bit-compatible with this entry point).
+ * adamw_ema_step: p, g, m, v and (nullable) ema are f32 [n], 16-byte aligned.  Per element, every operation an IEEE f32 operation
+ * rounded on its own (the file is compiled without contraction; tests/optim_twin.py restates it):
+ *     gr = g * gscale                                   gscale = *scale_dev when scale_dev is given (4-byte aligned), else grad_scale
+ *     m  = beta1 * m + (1.f - beta1) * gr
+ *     v  = beta2 * v + ((1.f - beta2) * gr) * gr
+ *     p  = p * decay_s                                  decay_s = (float)(1.0 - (double)lr * (double)wd_s), s = the element's segment
+ *     p  = p - (lr_bc1 * m) / (sqrtf(v) * inv_sqrt_bc2 + eps)
+ *     e  = ema_decay * e + one_m_d * p                  only with ema; one_m_d = (float)(1.0 - (double)ema_decay), 0 <= ema_decay < 1
+ * with lr_bc1 = (float)(lr / (1 - beta1^step)) and inv_sqrt_bc2 = (float)(1 / sqrt(1 - beta2^step)) formed in double as maavss_adam_step
+ * forms them; `step` is the 1-based step count.  wd_s = 0 gives decay_s == 1.0f and p * 1 == p: undecayed tensors take no branch.
+ * Decay table (HOST arrays, copied into the launch arguments: no device table, no staging copy): host_seg_end [n_seg] = the segment
+ * ends in elements relative to p, ascending, multiples of 4, the last one >= n; host_seg_wd [n_seg] = the weight decay of each segment,
+ * finite and >= 0; 1 <= n_seg <= 64 -- the caller splits a run with more (maavss_amd.trainer.plan_launches).
+ * Skip: with skip_nonfinite != 0 the kernel reads *norm_dev (f32, what maavss_tensor_stats left on the stream) and, when it is NaN or
+ * an infinity, every thread returns before its first store: p, m, v and ema keep their bytes.  With count_skip != 0 (needs
+ * skip_nonfinite and skipped) thread 0 of workgroup 0 then adds 1 to *skipped with a plain load and store: exactly one launch of a step
+ * carries the flag and launches on a stream are ordered.  Deviation from torch.cuda.amp.GradScaler, which leaves a skipped step out of
+ * the optimizer's step count: `step` is the caller's count, and maavss_amd.FusedAdam advances it (and its learning-rate schedule) on a
+ * skipped step too -- the bias correction moves on by one step while the moments do not move.
+ * Every argument is checked before the launch.  No float atomics: two runs give identical bytes.
+ * swap_f32: exchanges a [n] and b [n] in place (16-byte aligned, not overlapping): the weights and their average around a validation
+ * pass, without a third buffer. */
+int maavss_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                          float eps, int64_t step, float grad_scale, const float* scale_dev, const float* norm_dev,
+                          int skip_nonfinite, int* skipped, int count_skip, const int64_t* host_seg_end, const float* host_seg_wd,
+                          int n_seg, float ema_decay, void* stream);
+int maavss_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* ---- EXTENSION: per-tensor statistics of a flat f32 buffer (maavss_amd.TensorStats, gradient-norm clipping, ModelWatch) ------
  * What torch.nn.utils.clip_grad_norm_ and wandb.watch(model, log="all") (train_avse_frames.py:108) compute through autograd hooks,
  * for the autograd-free step: one segmented reduction over the flat gradient (or parameter) buffer.  Added without a version bump.

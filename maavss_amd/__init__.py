@@ -9,6 +9,7 @@ from .avse import AV_Fusion_Model_Frames  # noqa: F401
 from .avfm import AV_Fusion_Model  # noqa: F401
 from .phasegram import video_phasegram  # noqa: F401
 from .trainer import FusedAdam, GradSync, TrainStep, shard_batch  # noqa: F401
+from .schedule import LRSchedule  # noqa: F401
 from .video_attention import VideoAttention  # noqa: F401
 from .checkpoint import latest_file, load_checkpoint, save_checkpoint, save_model  # noqa: F401
 from .pipeline import ClipPipeline  # noqa: F401

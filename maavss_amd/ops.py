@@ -554,6 +554,34 @@ def adam_step_dscale(p, g, m, v, lr, step, grad_scale_dev, betas=(0.9, 0.999), e
          float(eps), int(step), ptr(grad_scale_dev), stream_ptr())
 
 
+ADAMW_MAX_SEGMENTS = 64      # capacity of the decay table one maavss_adamw_ema_step launch carries in its arguments
+
+
+def adamw_ema_step(p, g, m, v, lr, step, seg_ends, seg_wd, ema=None, ema_decay=0.0, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0,
+                   scale_dev=None, norm_dev=None, skipped=None, count_skip=False):
+    """One AdamW (+ weight average) update of a contiguous run (include/maavss.h: maavss_adamw_ema_step).  `seg_ends` / `seg_wd`: the
+    run's decay table on the host -- segment ends in elements relative to `p` (ascending multiples of 4, the last >= p.numel()) and the
+    weight decay of each, at most ADAMW_MAX_SEGMENTS of them.  `scale_dev` (f32 [1]) replaces `grad_scale`; `norm_dev` (f32 [1]) turns the
+    non-finite skip on; `skipped` (int32 [1]) is counted up by this launch when `count_skip`."""
+    _f32(p, g, m, v, ema, scale_dev, norm_dev)
+    if skipped is not None:
+        _lib.require_cuda(skipped)
+        assert skipped.dtype == torch.int32
+    ends = (ctypes.c_int64 * len(seg_ends))(*[int(e) for e in seg_ends])
+    wds = (ctypes.c_float * len(seg_wd))(*[float(w) for w in seg_wd])
+    assert len(seg_ends) == len(seg_wd)
+    call("maavss_adamw_ema_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+         float(eps), int(step), float(grad_scale), ptr(scale_dev), ptr(norm_dev), int(norm_dev is not None), ptr(skipped),
+         int(bool(count_skip)), ctypes.addressof(ends), ctypes.addressof(wds), len(seg_ends), float(ema_decay), stream_ptr())
+
+
+def swap_f32(a, b):
+    """In-place exchange of two f32 buffers of equal length (no third buffer, no synchronisation)."""
+    _f32(a, b)
+    assert a.numel() == b.numel() and a.is_contiguous() and b.is_contiguous()
+    call("maavss_swap_f32", ptr(a), ptr(b), a.numel(), stream_ptr())
+
+
 def f32_to_bf16(src, dst):
     """bf16 wire format of the gradient all-reduce: dst (bf16) = round(src (f32)); length a multiple of 8."""
     _lib.require_cuda(src, dst)

@@ -92,6 +92,63 @@ class FlatParams:
                 self.touched.add(n)
 
 
+def _numel(shape):
+    k = 1
+    for d in shape:
+        k *= d
+    return k
+
+
+def default_decay_filter(name, param):
+    """The tensors AdamW's decay applies to by default: everything with two or more dimensions (conv and linear weights, the LSTM's
+    weight_ih / weight_hh); biases and BatchNorm weight and bias are left out."""
+    return param.ndim >= 2
+
+
+def plan_launches(runs, flat, weight_decay, max_segments=None):
+    """Pure planning of the maavss_adamw_ema_step launches: `runs` as FusedAdam._runs() gives them, `weight_decay` {name: float}.
+    One decay-table segment per tensor (its 64-aligned extent); a run with more than `max_segments` (the table's capacity,
+    ops.ADAMW_MAX_SEGMENTS) tensors is split into consecutive launches.  -> [dict(lo, hi, step, names, ends, wd)]: `ends` are the
+    segment ends relative to `lo`, `hi` never passes flat.total."""
+    cap = ops.ADAMW_MAX_SEGMENTS if max_segments is None else int(max_segments)
+    if cap < 1:
+        raise ValueError("max_segments must be >= 1")
+    out = []
+    for lo, hi, st, names in runs:
+        for a in range(0, len(names), cap):
+            part = names[a:a + cap]
+            plo = flat.offsets[part[0]]
+            ends = [_align(flat.offsets[n] + _numel(flat.shapes[n])) - plo for n in part]
+            out.append(dict(lo=plo, hi=min(plo + ends[-1], flat.total), step=st, names=list(part), ends=ends,
+                            wd=[float(weight_decay.get(n, 0.0)) for n in part]))
+    return out
+
+
+class _EmaWeights:
+    """Context manager of FusedAdam.ema_weights(): two launches of the swap kernel, no synchronisation."""
+
+    def __init__(self, opt):
+        self.opt = opt
+
+    def __enter__(self):
+        from ._lib import MaavssError
+        o = self.opt
+        if o.ema is None:
+            raise MaavssError("ema_weights(): this optimizer keeps no weight average (ema_decay=None)")
+        if o._ema_swapped:
+            raise MaavssError("ema_weights() is not re-entrant: the averaged weights are already in the parameter buffer")
+        o.flat.check_links()
+        ops.swap_f32(o.flat.params, o.ema)
+        o._ema_swapped = True
+        return o
+
+    def __exit__(self, *exc):
+        o = self.opt
+        ops.swap_f32(o.flat.params, o.ema)
+        o._ema_swapped = False
+        return False
+
+
 class FusedAdam:
     """torch.optim.Adam semantics (betas .9/.999, eps 1e-8, no weight decay, no amsgrad) in HIP launches over the flat
     buffers.  Like torch, a parameter is only stepped when a backward pass produced a gradient for it since the last
@@ -105,13 +162,50 @@ class FusedAdam:
     coefficient from there -- no host synchronisation.  Unlike torch, the gradients are NOT rescaled in memory: `flat.grads` keeps the
     unclipped values, the scale is applied inside the Adam kernel.  `grad_norm` (the norm of grad_scale * g) and `clip_scale`
     (grad_scale * min(1, max_grad_norm / (norm + 1e-6))) are the device scalars of the last step; a non-finite gradient makes them
-    NaN (any NaN) or +inf / 0 (an inf, no NaN), as torch's error_if_nonfinite=False -- the caller decides when to look."""
+    NaN (any NaN) or +inf / 0 (an inf, no NaN), as torch's error_if_nonfinite=False -- the caller decides when to look.
 
-    def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
+    Beyond the reference (all off by default: step() then issues exactly the launches above; with any of `weight_decay`, `ema_decay`,
+    `skip_nonfinite` set, every run goes through maavss_adamw_ema_step instead -- one kernel that decays, steps and averages):
+
+    * `weight_decay`, `decay_filter(name, param) -> bool`: torch.optim.AdamW's decoupled decay, p *= 1 - lr * weight_decay before the
+      Adam update, on the tensors the filter accepts (default_decay_filter: ndim >= 2).  state_dict() reports the decay in torch's
+      one-group layout and loads into torch.optim.AdamW; the filter is code and is not stored (torch would decay every tensor).
+    * `ema_decay` d in [0, 1): a second flat buffer `ema` = d * ema + (1 - d) * p after every update, a copy of the weights when the
+      optimizer is built and after ema_reset().  Only stepped runs update it: a frozen tensor's average stays equal to its weights.
+      `ema_warmup`: update number t (from 0) uses min(d, (1 + t) / (10 + t)).  ema_state_dict() / load_ema_state_dict() and the
+      ema_weights() context manager give access.  BatchNorm running statistics are buffers, not parameters: they are not averaged, and
+      inside ema_weights() the model runs the averaged weights with the LIVE running statistics.
+    * `skip_nonfinite`: a step whose gradient norm (grad_norm, from the same reduction clipping uses; with max_grad_norm=None it runs
+      with max_norm = inf) is NaN or infinite leaves weights, moments and average untouched, decided on the device without a host
+      synchronisation.  `skipped_steps` is a device int32 [1], read when the caller chooses.  Deviation from torch.cuda.amp.GradScaler:
+      a skipped step still advances the host step counts, the average's update count and the schedule -- the bias correction moves on by
+      one step while the moments do not move.
+    * `lr` may be a maavss_amd.LRSchedule: every step() takes the next rate from it; `lr` / the param group's "lr" is then the rate
+      of the last step."""
+
+    def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, weight_decay=0.0, decay_filter=None,
+                 ema_decay=None, ema_warmup=False, skip_nonfinite=False):
+        from .schedule import LRSchedule
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else FlatParams(model_or_flat)
+        self.schedule = lr if isinstance(lr, LRSchedule) else None
+        if self.schedule is not None:
+            lr = self.schedule.lr(self.schedule.t)
         self.lr, self.betas, self.eps = lr, betas, eps
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError("max_grad_norm must be None or >= 0")
+        if not 0.0 <= float(weight_decay) < float("inf"):
+            raise ValueError("weight_decay must be finite and >= 0")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must be None or in [0, 1)")
+        self.weight_decay = float(weight_decay)
+        self.decay_filter = default_decay_filter if decay_filter is None else decay_filter
+        self._decayed = None                    # {name: the filter's answer}, asked once, when first needed
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup, self.skip_nonfinite = bool(ema_warmup), bool(skip_nonfinite)
+        self.ema = None if ema_decay is None else self.flat.params.clone()
+        self.ema_updates = 0
+        self._ema_swapped = False
+        self.skipped_steps = torch.zeros(1, dtype=torch.int32, device=self.flat.params.device) if skip_nonfinite else None
         self.max_grad_norm = max_grad_norm
         self.grad_stats = None                  # tensor_stats.TensorStats over flat.grads, built by the first clipped step
         self.grad_norm = self.clip_scale = None
@@ -151,16 +245,61 @@ class FusedAdam:
             for n in names:
                 self.steps[n] = st
 
+    @property
+    def decayed(self):
+        """{parameter name: whether weight_decay applies to it} -- decay_filter(name, param) of every tensor of the layout."""
+        if self._decayed is None:
+            self._decayed = {n: bool(self.decay_filter(n, self.flat.tensors[n])) for n in self.flat.names}
+        return self._decayed
+
+    @property
+    def extended(self):
+        """True when step() goes through maavss_adamw_ema_step (any of weight decay, weight average, non-finite skip is on)."""
+        return self.weight_decay != 0.0 or self.ema is not None or self.skip_nonfinite
+
+    def _next_ema_decay(self):
+        """The decay of average update number `ema_updates` (host arithmetic)."""
+        t = self.ema_updates
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+
+    def _step_extended(self, runs, grad_scale):
+        f = self.flat
+        with_norm = self.max_grad_norm is not None or self.skip_nonfinite
+        wd = {n: self.weight_decay for n in f.names if self.decayed[n]}
+        launches = plan_launches(runs, f, wd)
+        d = self._next_ema_decay() if self.ema is not None else 0.0
+        for k, ln in enumerate(launches):
+            lo, hi = ln["lo"], ln["hi"]
+            ops.adamw_ema_step(f.params[lo:hi], f.grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr, ln["step"],
+                               ln["ends"], ln["wd"], ema=None if self.ema is None else self.ema[lo:hi], ema_decay=d, betas=self.betas,
+                               eps=self.eps, grad_scale=grad_scale, scale_dev=self.clip_scale if with_norm else None,
+                               norm_dev=self.grad_norm if self.skip_nonfinite else None, skipped=self.skipped_steps,
+                               count_skip=self.skip_nonfinite and k == 0)
+        if self.ema is not None and launches:
+            self.ema_updates += 1
+
     def step(self, grad_scale=1.0):
+        if self._ema_swapped:
+            from ._lib import MaavssError
+            raise MaavssError("step() inside ema_weights(): the parameter buffer holds the averaged weights")
         self.flat.check_links()
         runs = self._runs()
-        if self.max_grad_norm is not None and runs:
+        if self.schedule is not None:
+            self.lr = self.schedule.next_lr()
+        extended = self.extended
+        if (self.max_grad_norm is not None or self.skip_nonfinite) and runs:
             if self.grad_stats is None:
                 from .tensor_stats import TensorStats
                 self.grad_stats = TensorStats(self.flat, bins=1)
+            # without clipping, max_norm = inf: the coefficient min(1, inf / (norm + 1e-6)) is 1 for every finite norm, scale = grad_scale
             out = self.grad_stats.run(self.flat.grads, names=[n for r in runs for n in r[3]], hist=False,
-                                      max_norm=self.max_grad_norm, grad_scale=grad_scale)
+                                      max_norm=self.max_grad_norm if self.max_grad_norm is not None else float("inf"),
+                                      grad_scale=grad_scale)
             self.grad_norm, self.clip_scale = out["norm"], out["scale"]
+        if extended:
+            self._step_extended(runs, grad_scale)
+            self._commit(runs)
+            return
         for lo, hi, st, _ in runs:
             hi = min(hi, self.flat.total)
             if self.max_grad_norm is not None:
@@ -193,14 +332,62 @@ class FusedAdam:
             state[i] = {"step": torch.tensor(float(self.steps[n])),
                         "exp_avg": self.exp_avg[o:o + k].view(f.shapes[n]).clone(),
                         "exp_avg_sq": self.exp_avg_sq[o:o + k].view(f.shapes[n]).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay if self.weight_decay else 0,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(f.torch_order)))}
+        if self.weight_decay:
+            group["decoupled_weight_decay"] = True      # torch.optim.AdamW's marker: without it torch reads the decay as Adam's L2 term
         return {"state": state, "param_groups": [group]}
+
+    def ema_reset(self):
+        """The average starts over as a copy of the current weights (update count 0)."""
+        from ._lib import MaavssError
+        if self.ema is None:
+            raise MaavssError("ema_reset(): this optimizer keeps no weight average (ema_decay=None)")
+        if self._ema_swapped:
+            raise MaavssError("ema_reset() inside ema_weights()")
+        self.ema.copy_(self.flat.params)
+        self.ema_updates = 0
+
+    def ema_weights(self):
+        """Context manager: inside the block the flat parameter buffer -- hence the model, Validator, Enhancer and model.state_dict()
+        -- holds the averaged weights and `ema` holds the raw ones; they are swapped back on exit.  Two launches of
+        maavss_swap_f32, no third buffer, no synchronisation.  BatchNorm running statistics are buffers and stay the live ones.
+        Nesting the context and calling step() inside it raise."""
+        return _EmaWeights(self)
+
+    def ema_state_dict(self):
+        """{parameter name: averaged tensor} in the keys of model.state_dict(), plus "num_updates"."""
+        from ._lib import MaavssError
+        if self.ema is None:
+            raise MaavssError("ema_state_dict(): this optimizer keeps no weight average (ema_decay=None)")
+        f = self.flat
+        src = f.params if self._ema_swapped else self.ema
+        sd = {n: src[f.offsets[n]:f.offsets[n] + _numel(f.shapes[n])].view(f.shapes[n]).clone() for n in f.torch_order}
+        sd["num_updates"] = torch.tensor(self.ema_updates, dtype=torch.int64)
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        from ._lib import MaavssError
+        if self.ema is None:
+            raise MaavssError("load_ema_state_dict(): this optimizer keeps no weight average (ema_decay=None)")
+        if self._ema_swapped:
+            raise MaavssError("load_ema_state_dict() inside ema_weights()")
+        f = self.flat
+        for n in f.torch_order:
+            if n not in sd:
+                raise ValueError(f"averaged weights: no entry for parameter {n}")
+            if tuple(sd[n].shape) != f.shapes[n]:
+                raise ValueError(f"averaged weights of {n} have shape {tuple(sd[n].shape)}, expected {f.shapes[n]}")
+        for n in f.torch_order:
+            self.ema[f.offsets[n]:f.offsets[n] + _numel(f.shapes[n])].copy_(sd[n].reshape(-1))
+        self.ema_updates = int(sd.get("num_updates", 0))
 
     def load_state_dict(self, sd):
         """Accepts the dict above and a reference checkpoint's torch.optim.Adam state (parameters the reference never
-        stepped -- stft_decoder.* under forward() -- have no entry there: their moments and step count stay zero)."""
+        stepped -- stft_decoder.* under forward() -- have no entry there: their moments and step count stay zero).  Like torch, the
+        group's lr, betas, eps and weight_decay replace the constructor's (a torch.optim.AdamW state brings its decay along; a non-zero
+        decay of plain torch.optim.Adam, the L2 form, is refused).  With a schedule, the next step takes its rate from the schedule again."""
         f = self.flat
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(f.torch_order):
@@ -209,6 +396,10 @@ class FusedAdam:
         self.lr = float(groups[0]["lr"])
         self.betas = tuple(float(b) for b in groups[0]["betas"])
         self.eps = float(groups[0]["eps"])
+        wd = float(groups[0].get("weight_decay", 0))
+        if wd != 0.0 and not groups[0].get("decoupled_weight_decay", False):
+            raise ValueError(f"optimizer state has weight_decay {wd} as torch.optim.Adam's L2 term; only AdamW's decoupled decay is implemented")
+        self.weight_decay = wd
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()
         self.steps = {n: 0 for n in f.names}
@@ -378,21 +569,28 @@ class TrainStep:
     """One optimizer step of the fusion network, autograd-free (see module docstring)."""
 
     def __init__(self, model, lr=1e-5, loss_coeff=0.001, num_seq=1, betas=(0.9, 0.999), eps=1e-8,
-                 process_group=None, sync_bn=False, grad_wire_dtype=None, max_grad_norm=None, audio_loss=None):
+                 process_group=None, sync_bn=False, grad_wire_dtype=None, max_grad_norm=None, audio_loss=None, weight_decay=0.0,
+                 decay_filter=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False):
         """`audio_loss`: None trains on the reference's MSE of the STFT planes (ops.mse_pair); a maavss_amd.SpectralLoss replaces that
         term by the power-law compressed spectral loss (ops.spectral_loss_pair): `losses` keeps its three positions (losses[0] is the
         new audio loss, losses[1] the attention MSE by mse_pair's own kernel) and `loss_parts` holds the magnitude and the complex
         mean (device f64 [2]) that losses[0] mixes.
         `max_grad_norm`: FusedAdam's gradient-norm clipping.  It runs once per optimizer step, in the `last` window after the
         all-reduce has finished, on the accumulated, summed gradient times 1 / world -- the norm of the AVERAGED gradient, as DDP
-        followed by clip_grad_norm_ gives; every rank computes it from identical bytes, so there is no extra collective."""
+        followed by clip_grad_norm_ gives; every rank computes it from identical bytes, so there is no extra collective.
+        `lr` (a float or a maavss_amd.LRSchedule), `weight_decay`, `decay_filter`, `ema_decay`, `ema_warmup`, `skip_nonfinite`: FusedAdam's
+        (not in the reference; all off by default).  The skip is decided from the same all-reduced gradient bytes on every rank, so the
+        ranks agree without a collective."""
         self.model = model
         self.flat = FlatParams(model)
-        self.opt = FusedAdam(self.flat, lr, betas, eps, max_grad_norm=max_grad_norm)
+        self.opt = FusedAdam(self.flat, lr, betas, eps, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_filter=decay_filter,
+                             ema_decay=ema_decay, ema_warmup=ema_warmup, skip_nonfinite=skip_nonfinite)
         self.loss_coeff, self.num_seq = loss_coeff, num_seq
         self.sync = GradSync(self.flat.grads, self.flat.fusion_end, process_group, flat=self.flat, wire_dtype=grad_wire_dtype)
         # replicas start identical: rank 0's weights (one flat buffer) and BatchNorm buffers, like DDP's constructor
         self.sync.broadcast([self.flat.params] + [b for _, b in model.named_buffers()])
+        if self.opt.ema is not None and self.sync.enabled:
+            self.opt.ema_reset()                      # the average starts from the broadcast weights
         if sync_bn and self.sync.enabled:
             model.set_bn_sync(self.sync.sum_)
         if audio_loss is not None and not isinstance(audio_loss, SpectralLoss):
@@ -428,6 +626,10 @@ class TrainStep:
             if optimizer_step:
                 self.opt.step(grad_scale=1.0 / self.sync.world)
         return self.losses
+
+    def ema_weights(self):
+        """FusedAdam.ema_weights(): inside the block the model runs the averaged weights (and the live BatchNorm statistics)."""
+        return self.opt.ema_weights()
 
     def sliding_window_step(self, x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, collect=False):
         """The reference's optimizer step over `num_seq` overlapping windows (train_avse_frames.py:143-181):
