@@ -152,3 +152,28 @@ def require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
             raise MaavssError("maavss_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
+
+
+def wave_rows(t, what):
+    """t: a float32 tensor [L] or [B, L] -> [B, L] with contiguous samples and a row stride >= 0 (copied only where it is not so)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (1, 2):
+        raise ValueError(f"{what} must be a float32 tensor [L] or [B, L], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+    t = t[None] if t.dim() == 1 else t
+    if t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{what} is empty: {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < 0:
+        t = t.contiguous()
+    return t
+
+
+def require_same_shape(est, ref):
+    if est.shape != ref.shape:
+        raise ValueError(f"est {tuple(est.shape)} and ref {tuple(ref.shape)} differ in shape")
+
+
+def column_dict(out, names):
+    """out [B, len(names)] -> {name: its column} and "raw": out, the one buffer they are views of."""
+    res = {k: out[:, i] for i, k in enumerate(names)}
+    res["raw"] = out
+    return res

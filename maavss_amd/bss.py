@@ -6,24 +6,13 @@ definition next to maavss_bss_eval; tests/bss_twin.py is its float64 restatement
 Nothing here waits for the device: `Validator(bss_filter=...)` accumulates the scores, `Validator.result()` copies them."""
 import torch
 
-from ._lib import call, ptr, query, require_cuda, stream_ptr, workspace
+from ._lib import call, column_dict, ptr, query, require_cuda, require_same_shape, stream_ptr, wave_rows, workspace
 
 BSS_COLUMNS = ("s_tt", "s_ee", "s_ii", "s_aa", "s_pp", "sdr_db", "sir_db", "sar_db", "n_sources", "status")
 BSS_DB = ("sdr_db", "sir_db", "sar_db")                  # columns 5..7 of a bss_eval_metrics row
 BSS_MAX_FILTER = 512
 BSS_MAX_OTHERS = 3
 BSS_WORKSPACE_CAP = 1 << 30          # bytes: a batch whose workspace would be larger is processed in groups of rows
-
-
-def _rows(t, what):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (1, 2):
-        raise ValueError(f"{what} must be a float32 tensor [L] or [B, L], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
-    t = t[None] if t.dim() == 1 else t
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what} is empty: {tuple(t.shape)}")
-    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < 0:
-        t = t.contiguous()
-    return t
 
 
 def _sources(t, b, n):
@@ -52,9 +41,8 @@ def bss_eval_metrics(est, ref, others=None, filt_len=BSS_MAX_FILTER):
     scores of such a row are NaN), and "raw" [B, 10], the one buffer they are columns of.  A batch whose workspace would exceed
     BSS_WORKSPACE_CAP (1 GiB; a row of 1024 unknowns takes 9 MB, of 2048 35 MB) is processed in groups of rows; every row is computed on
     its own, so the grouping does not change a bit.  Only enqueues launches on the current stream."""
-    est, ref = _rows(est, "est"), _rows(ref, "ref")
-    if est.shape != ref.shape:
-        raise ValueError(f"est {tuple(est.shape)} and ref {tuple(ref.shape)} differ in shape")
+    est, ref = wave_rows(est, "est"), wave_rows(ref, "ref")
+    require_same_shape(est, ref)
     b, n = est.shape
     if isinstance(filt_len, bool) or not isinstance(filt_len, int) or not 1 <= filt_len <= BSS_MAX_FILTER:
         raise ValueError(f"filt_len must be an integer in 1..{BSS_MAX_FILTER}, got {filt_len!r}")
@@ -76,6 +64,4 @@ def bss_eval_metrics(est, ref, others=None, filt_len=BSS_MAX_FILTER):
         o = None if oth is None else oth[g0:g1]
         call("maavss_bss_eval", ptr(est[g0:g1]), est.stride(0), ptr(ref[g0:g1]), ref.stride(0), ptr(o), 0 if o is None else o.stride(0),
              0 if o is None else o.stride(1), k, g1 - g0, n, filt_len, ptr(out[g0:g1]), ptr(ws), nbytes, st)
-    res = {name: out[:, i] for i, name in enumerate(BSS_COLUMNS)}
-    res["raw"] = out
-    return res
+    return column_dict(out, BSS_COLUMNS)

@@ -24,6 +24,7 @@
 // this file with -ffp-contract=off; the fma() calls are the fusions there are.
 // Plain f64 VALU arithmetic: the MFMA f64 instructions were not tried (HISTORY.md gives the measured times per stage).
 #include "common.h"
+#include "metric_f64.h"
 
 #define BS_LMAX 512
 #define BS_KMAX 3
@@ -76,7 +77,6 @@ static inline bs_plan bs_make_plan(int64_t rows, int64_t N, int K, int L) {
   return p;
 }
 
-__device__ __forceinline__ double bs_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 // the value lane `lane` (uniform over the wave) holds
 __device__ __forceinline__ double bs_readlane_d(double v, int lane) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(64) void bss_finalize_kernel(const double* __restri
   const int status = m[1];
   if (status != 0) {
     if (lane == 0) {
-      for (int q = 0; q < 8; ++q) o[q] = bs_nan();
+      for (int q = 0; q < 8; ++q) o[q] = nan_d();
       o[8] = (double)m[0];
       o[9] = (double)status;
     }

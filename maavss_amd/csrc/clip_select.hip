@@ -15,6 +15,7 @@
 //                      where neighbouring workgroups run together) and 8 B a pair; writes 52 B a clip.
 //   cs_select          one thread per clip: the table against the thresholds -> one reason byte.  Reads 44 B, writes 1 B a clip.
 #include "common.h"
+#include "metric_f64.h"
 #include "bank_load.h"      // bank_load (both storages), bank_clamp
 
 namespace {
@@ -22,8 +23,6 @@ namespace {
 constexpr int CS_MAX_J = 2048;          // segments of a clip the clip kernel keeps in LDS (16 KiB of f64)
 constexpr int CS_CHUNK = 16384;         // samples per partial of the recording level
 constexpr int64_t CS_MAX_CHUNKS = 65535;      // chunks of one recording: the grid's y extent
-
-__device__ __forceinline__ bool cs_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
 // rec_tab int64 [3][n_rec]: first sample, samples, first partial slot
 __global__ __launch_bounds__(256) void cs_level_partial_kernel(const float* __restrict__ audio, int64_t n_samples,
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(256) void cs_level_partial_kernel(const float* __re
   double s = 0.0;
   for (int64_t i = threadIdx.x; i < count; i += 256) {
     const float x = p[i];
-    const double xd = cs_nonfinite(x) ? 0.0 : (double)x;
+    const double xd = f32_nonfinite(x) ? 0.0 : (double)x;
     s += xd * xd;
   }
   s = wg_reduce<WG_THREAD0, WG_SUM>(wave_sum_d(s), red, threadIdx.x >> 6, threadIdx.x & 63);
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(256) void cs_clip_kernel(const float* __restrict__ 
       const double xd = (double)x;
       e += xd * xd;
       pk = fmaxf(pk, fabsf(x));                               // fmaxf drops a NaN: the peak is over the samples that are numbers
-      cnt[0] += cs_nonfinite(x) ? 1 : 0;
+      cnt[0] += f32_nonfinite(x) ? 1 : 0;
     }
     e = wave_sum_d(e);
     if (lane == 0) E[j] = e;
@@ -128,8 +127,8 @@ __global__ __launch_bounds__(256) void cs_clip_kernel(const float* __restrict__ 
   out.rms_db[b] = 10.0 * log10(mean);
   out.rel_db[b] = 10.0 * log10(mean / rec_power);
   out.peak[b] = pk;
-  out.n_bad[b] = (red_i[0][0] + red_i[1][0]) + (red_i[2][0] + red_i[3][0]);
-  out.n_active[b] = (red_i[0][1] + red_i[1][1]) + (red_i[2][1] + red_i[3][1]);
+  out.n_bad[b] = wg_col<WG_SUM>(red_i, 0);
+  out.n_active[b] = wg_col<WG_SUM>(red_i, 1);
   double msum = 0.0, mmax = 0.0;
   if (T > 1) {
     const int64_t v = bank_clamp(clip_frame[b], n_frames - T);

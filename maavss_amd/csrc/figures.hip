@@ -9,7 +9,7 @@
 //                     every thread makes four consecutive output pixels and stores them as one 16-byte word.  Element strides, transpose,
 //                     row flip and integer nearest replication are index arithmetic: no copy of the image is made
 //   specgram          one workgroup per (row, segment) of matplotlib's Axes.specgram(mode='magnitude' | 'phase') with its defaults: the
-//                     Hann-windowed segment in LDS as f64, a radix-2 transform in the pattern of stoi_bands_kernel, 20 log10(|F| / sum w)
+//                     Hann-windowed segment in LDS as f64, a radix-2 transform (the butterfly of metric_f64.h), 20 log10(|F| / sum w)
 //                     and atan2 per bin, then np.unwrap along the column inside the workgroup: the corrections in parallel, their running
 //                     sum by one thread in bin order (numpy's cumsum order; two runs give the same bytes)
 //   filmstrip_max     64 workgroups per tensor: partial maxima of the target attention, the predicted attention and the video (torch.max);
@@ -19,40 +19,22 @@
 // The Makefile compiles this file with -ffp-contract=off: the three f64 operations of the colour mapping are then the twin's, and
 // viridis_colour is bit-exact against it on every element.
 #include "common.h"
+#include "metric_f64.h"
 #include "viridis_lut.h"
 
 #define SG_MAX 1024                  // the largest transform: 8 KB of f64 per LDS array
 #define SG_PI 3.141592653589793      // np.pi
 #define SG_2PI 6.283185307179586     // 2 * np.pi
 
-__device__ __forceinline__ double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ double fig_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-
 // one workgroup per image: range[2 n] = min, range[2 n + 1] = max over the finite elements (+inf, -inf when there is none)
 template <typename T>
 __global__ __launch_bounds__(256) void viridis_range_kernel(const T* __restrict__ x, int64_t H, int64_t W, int64_t sn, int64_t sh, int64_t sw,
                                                             double* __restrict__ range) {
-  __shared__ double red_lo[4], red_hi[4];
+  __shared__ double red[4][2];
   const int64_t n = blockIdx.x;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const T* __restrict__ img = x + n * sn;
-  double lo = fig_inf(), hi = -fig_inf();
+  double lo = inf_d(), hi = -inf_d();
   const int64_t count = H * W;
   for (int64_t e = tid; e < count; e += 256) {
     const double v = (double)img[(e / W) * sh + (e % W) * sw];
@@ -61,20 +43,12 @@ __global__ __launch_bounds__(256) void viridis_range_kernel(const T* __restrict_
       hi = v > hi ? v : hi;
     }
   }
-  lo = wave_min_d(lo);
-  hi = wave_max_d(hi);
-  if (lane == 0) {
-    red_lo[wave] = lo;
-    red_hi[wave] = hi;
-  }
+  const double v[2] = {wave_min_d(lo), wave_max_d(hi)};
+  wg_park(red, v, tid >> 6, tid & 63);
   __syncthreads();
   if (tid == 0) {
-    for (int q = 1; q < 4; ++q) {
-      lo = red_lo[q] < lo ? red_lo[q] : lo;
-      hi = red_hi[q] > hi ? red_hi[q] : hi;
-    }
-    range[2 * n] = lo;
-    range[2 * n + 1] = hi;
+    range[2 * n] = wg_col<WG_MIN>(red, 0);
+    range[2 * n + 1] = wg_col<WG_MAX>(red, 1);
   }
 }
 
@@ -174,17 +148,10 @@ __global__ __launch_bounds__(256) void specgram_kernel(const float* __restrict__
   ws = wave_sum_d(ws);
   ws = wg_reduce<WG_ALL, WG_SUM>(ws, red, wv, lane);            // its barrier also covers zr, zi and the twiddles
   for (int s = 0; s < lg; ++s) {
-    const int half = 1 << s;
     for (int b = t; b < half_n; b += 256) {
-      const int j = b & (half - 1);
-      const int i0 = ((b >> s) << (s + 1)) + j, i1 = i0 + half;
-      const double c = twc[j << (lg - 1 - s)], sn = tws[j << (lg - 1 - s)];
-      const double ur = zr[i0], ui = zi[i0], vr = zr[i1], vi = zi[i1];
-      const double pr = c * vr + sn * vi, pi = c * vi - sn * vr;      // (c - i sn) (vr + i vi)
-      zr[i0] = ur + pr;
-      zi[i0] = ui + pi;
-      zr[i1] = ur - pr;
-      zi[i1] = ui - pi;
+      int i0, i1, j;
+      fft2_index(b, s, i0, i1, j);
+      fft2_rotate_add(zr, zi, i0, i1, twc[j << (lg - 1 - s)], tws[j << (lg - 1 - s)]);
     }
     __syncthreads();
   }

@@ -17,6 +17,7 @@
 // file with -ffp-contract=off (under the library's -ffp-contract=fast the backend fuses across `#pragma clang fp contract(off)`); the
 // explicit fma() calls are on exact products of f32 values, where fused and unfused give the same bits.
 #include "common.h"
+#include "metric_f64.h"
 
 #define WM_CH 4096           // chunk length in samples: one 60 s recording (960 000 samples) is 235 workgroups; a wave reduces several
                              // frames before the per-workgroup log10 and wave sums (at 1024 those were 9/10 of pass 1's time)
@@ -30,8 +31,6 @@ static_assert(sizeof(wm_partial) == 48, "workspace layout of include/maavss.h");
 
 static inline int wm_chunk_len(int seg_len) { return WM_CH / seg_len * seg_len; }
 static inline int64_t wm_chunks_per_row(int64_t L, int seg_len) { return (L + wm_chunk_len(seg_len) - 1) / wm_chunk_len(seg_len); }
-
-__device__ __forceinline__ double qm_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // sum over the G (a power of two <= 64) consecutive lanes a lane's group is made of; every lane of the group gets it
 __device__ __forceinline__ double qm_group_sum(double v, int G) {
@@ -114,15 +113,15 @@ __global__ __launch_bounds__(64) void wave_metrics_finalize1_kernel(const wm_par
   double* __restrict__ o = out + row * WM_COLS;
   // the squares of finite f32 values cannot overflow an f64 sum: Sxx + Syy is finite exactly when every sample of the row is
   if (!__builtin_isfinite(sxx + syy)) {
-    for (int k = 0; k < WM_COLS; ++k) o[k] = k == 8 ? 0.0 : qm_nan();
-    alpha[row] = qm_nan();
+    for (int k = 0; k < WM_COLS; ++k) o[k] = k == 8 ? 0.0 : nan_d();
+    alpha[row] = nan_d();
     return;
   }
   o[0] = sxx;
   o[1] = syy;
   o[2] = sxy;
   o[3] = see;
-  o[5] = sxx == 0.0 ? qm_nan() : 10.0 * log10(sxx / see);      // no reference, no ratio (0 / See = 0 would read -inf)
+  o[5] = sxx == 0.0 ? nan_d() : 10.0 * log10(sxx / see);      // no reference, no ratio (0 / See = 0 would read -inf)
   o[7] = seg / frames;                                          // 0 / 0 = NaN without a usable frame
   o[8] = frames;
   alpha[row] = sxy / sxx;
@@ -247,6 +246,12 @@ __global__ __launch_bounds__(64) void metric_add_classes_kernel(const double* __
   }
 }
 
+int rows_sum_launch(const double* partials, int64_t rows, int64_t per_row, int K, double div1, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)rows), dim3(64), 0, st, partials, per_row, K, div1, out);
+  MAAVSS_LAUNCH_CHECK("rows_sum_kernel");
+  return MAAVSS_OK;
+}
+
 extern "C" int maavss_wave_metrics_chunk(void) { return WM_CH; }
 
 extern "C" int64_t maavss_wave_metrics_ws_bytes(int64_t B, int64_t L, int seg_len) {
@@ -258,14 +263,9 @@ extern "C" int64_t maavss_wave_metrics_ws_bytes(int64_t B, int64_t L, int seg_le
 
 extern "C" int maavss_wave_metrics(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L,
                                    int seg_len, double* out, void* ws, int64_t ws_bytes, void* stream) {
-  MAAVSS_CHECK_ARG(est && ref && out && ws, "wave_metrics: null pointer");
+  if (int rc = metric_rows_check("wave_metrics", est, est_stride, ref, ref_stride, B, out, ws)) return rc;
   MAAVSS_CHECK_ARG(B > 0 && L > 0 && L < (int64_t)1 << 40, "wave_metrics: bad sizes (B %lld, L %lld)", (long long)B, (long long)L);
   MAAVSS_CHECK_ARG(seg_len >= 1 && seg_len <= WM_CH, "wave_metrics: seg_len must be in 1..%d (got %d)", WM_CH, seg_len);
-  MAAVSS_CHECK_ARG(B == 1 || (est_stride >= 0 && ref_stride >= 0 && est_stride < (int64_t)1 << 40 && ref_stride < (int64_t)1 << 40),
-                   "wave_metrics: row strides %lld, %lld: rows would not be addressable (strides are >= 0; rows may overlap)",
-                   (long long)est_stride, (long long)ref_stride);
-  MAAVSS_CHECK_ARG((((uintptr_t)est | (uintptr_t)ref) & 3) == 0, "wave_metrics: est and ref must be 4-byte aligned");
-  MAAVSS_CHECK_ARG((((uintptr_t)out | (uintptr_t)ws) & 7) == 0, "wave_metrics: out and workspace must be 8-byte aligned");
   const int64_t nch = wm_chunks_per_row(L, seg_len);
   MAAVSS_CHECK_ARG(nch <= (((int64_t)1 << 31) - 1) / B, "wave_metrics: %lld rows of %lld chunks are more workgroups than one launch takes",
                    (long long)B, (long long)nch);
@@ -311,9 +311,7 @@ extern "C" int maavss_spectrum_metrics(const float* pred, const float* tgt, int6
   hipLaunchKernelGGL(spectrum_metrics_frames_kernel, dim3((unsigned)((B * T + 3) / 4)), dim3(256), 0, st, pred, tgt, B * T, T, F, lsd_floor,
                      partials);
   MAAVSS_LAUNCH_CHECK("spectrum_metrics_frames_kernel");
-  hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, T, 2, (double)T, out);
-  MAAVSS_LAUNCH_CHECK("rows_sum_kernel");
-  return MAAVSS_OK;
+  return rows_sum_launch(partials, B, T, 2, (double)T, out, st);
 }
 
 extern "C" int maavss_sqerr_rows_chunk(void) { return SQ_CH; }
@@ -341,9 +339,7 @@ extern "C" int maavss_sqerr_rows(const float* pred, const float* tgt, int64_t B,
   hipLaunchKernelGGL(sqerr_scaled_chunks_kernel<false>, dim3((unsigned)(B * nch)), dim3(256), 0, st, pred, n, tgt, n, n, SQ_CH, nch,
                      (const double*)nullptr, partials);
   MAAVSS_LAUNCH_CHECK("sqerr_scaled_chunks_kernel");
-  hipLaunchKernelGGL(rows_sum_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, nch, 1, 1.0, out);
-  MAAVSS_LAUNCH_CHECK("rows_sum_kernel");
-  return MAAVSS_OK;
+  return rows_sum_launch(partials, B, nch, 1, 1.0, out, st);
 }
 
 extern "C" int maavss_metric_add_sum(const double* vals, int64_t n, int64_t stride, double weight, double* acc, void* stream) {

@@ -4,8 +4,10 @@
 //   wave_sum (f32), wave_sum_i, wave_max, wave_min    DPP on the VALU, result uniform across the wave
 //   wave_sum_d                                         f64 butterfly over __shfl_xor, offsets 32, 16, ..., 1; every lane gets the sum
 //   wave_strided_sum_d                                 lane l adds elements l, l + 64, ... in index order, then wave_sum_d
+//   wave_max_d, wave_min_d                             the same butterfly with a comparison (t > v ? t : v): a NaN is never picked up
 //   WG_SUM                                             the four per-wave results pairwise: (0 + 1) + (2 + 3)
-//   WG_MAX, WG_MIN                                     the NW per-wave results in wave index order: ((0, 1), 2), 3 ...
+//   WG_MAX, WG_MIN                                     the NW per-wave results in wave index order: ((0, 1), 2), 3 ...; f32 through
+//                                                      fmaxf / fminf, f64 through the comparison of wave_max_d / wave_min_d
 // The f32 sums that add their per-wave slots left to right (mse_partial_kernel, vit_cls_attn_kernel, the conv and batch-norm
 // partials) are a third order; they stay written out where they are.
 #pragma once
@@ -57,6 +59,22 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_min_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
 // sum of p[0], p[stride], ..., p[(count - 1) * stride] by one wave: lane l adds elements l, l + 64, ..., then the butterfly
 __device__ __forceinline__ double wave_strided_sum_d(const double* __restrict__ p, int64_t count, int64_t stride, int lane) {
   double s = 0.0;
@@ -79,6 +97,11 @@ __device__ __forceinline__ void wg_park(T (&red)[NW][N], const T (&v)[N], int wa
     for (int k = 0; k < N; ++k) red[wave][k] = v[k];
   }
 }
+// one step of WG_MAX / WG_MIN in the value's own type (fmaxf on a double would narrow it to f32)
+template <wg_op OP>
+__device__ __forceinline__ float wg_pick(float m, float t) { return OP == WG_MAX ? fmaxf(m, t) : fminf(m, t); }
+template <wg_op OP>
+__device__ __forceinline__ double wg_pick(double m, double t) { return OP == WG_MAX ? (t > m ? t : m) : (t < m ? t : m); }
 template <wg_op OP, int NW, int N, typename T>
 __device__ __forceinline__ T wg_col(const T (&red)[NW][N], int k) {
   if constexpr (OP == WG_SUM) {
@@ -87,7 +110,7 @@ __device__ __forceinline__ T wg_col(const T (&red)[NW][N], int k) {
   } else {
     T m = red[0][k];
 #pragma unroll
-    for (int q = 1; q < NW; ++q) m = OP == WG_MAX ? fmaxf(m, red[q][k]) : fminf(m, red[q][k]);
+    for (int q = 1; q < NW; ++q) m = wg_pick<OP>(m, red[q][k]);
     return m;
   }
 }

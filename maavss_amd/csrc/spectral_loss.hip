@@ -4,10 +4,12 @@
 // (the file is compiled with -ffp-contract=off): the differences M_p - M_t and p g_p - t g_t cancel, and in f32 they lose the result.
 //   spectral_loss_frames_kernel   one wave per (b, t) frame, four frames per workgroup: the frame's two sums to the workspace, and with
 //                                 GRAD the gradient, each element rounded once to f32
-//   spectral_loss_rows_kernel     one wave per row: the row's frames in index order -> rows [B][2]
+//   rows_sum_kernel               (quality_metrics.hip, through rows_sum_launch) one wave per row: the row's frames in index order
+//                                 -> rows [B][2]
 //   spectral_pair_finalize_kernel the rows in index order -> losses [3] and parts [2], next to mse_pair's attention term (mse_term.h)
 // No floating-point atomics: the same input gives the same bytes, and a row's bytes do not depend on the rows beside it.
 #include "common.h"
+#include "metric_f64.h"
 #include "mse_term.h"
 
 struct sl_params {
@@ -49,17 +51,6 @@ __global__ __launch_bounds__(256) void spectral_loss_frames_kernel(const float* 
   if (lane == 0) {
     partials[2 * bt] = mag;
     partials[2 * bt + 1] = cplx;
-  }
-}
-
-__global__ __launch_bounds__(64) void spectral_loss_rows_kernel(const double* __restrict__ partials, int64_t T, double* __restrict__ rows) {
-  const int64_t row = blockIdx.x;
-  const int lane = threadIdx.x;
-  const double mag = wave_strided_sum_d(partials + row * T * 2, T, 2, lane);
-  const double cplx = wave_strided_sum_d(partials + row * T * 2 + 1, T, 2, lane);
-  if (lane == 0) {
-    rows[2 * row] = mag;
-    rows[2 * row + 1] = cplx;
   }
 }
 
@@ -121,9 +112,7 @@ static int sl_launch(const float* pred, const float* tgt, int64_t B, int64_t T, 
   else
     hipLaunchKernelGGL(spectral_loss_frames_kernel<false>, grid, dim3(256), 0, st, pred, tgt, B * T, T, F, P, d_pred, partials);
   MAAVSS_LAUNCH_CHECK("spectral_loss_frames_kernel");
-  hipLaunchKernelGGL(spectral_loss_rows_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, T, rows);
-  MAAVSS_LAUNCH_CHECK("spectral_loss_rows_kernel");
-  return MAAVSS_OK;
+  return rows_sum_launch(partials, B, T, 2, 1.0, rows, st);      // s / 1.0 is s
 }
 
 extern "C" int maavss_spectral_loss(const float* pred, const float* tgt, int64_t B, int64_t T, int64_t F, double compress, double mix,

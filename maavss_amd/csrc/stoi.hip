@@ -21,6 +21,7 @@
 // -ffp-contract=off: the silence-free frames are then the twin's bit for bit (up to the last bit of cos), and what differs from the
 // twin is the order of sums and the transform's rounding.
 #include "common.h"
+#include "metric_f64.h"
 
 #define ST_FRAME 256
 #define ST_HOP 128
@@ -34,8 +35,6 @@
 
 // band j sums the bins [st_edge[j], st_edge[j + 1]): the bins of linspace(0, 10000, 513)[:257] nearest to 150 * 2^(j / 3) * 2^(-+1/6)
 __device__ const int st_edge[ST_J + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
-
-__device__ __forceinline__ double st_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 static inline int64_t st_frames(int64_t n) { return n > ST_FRAME ? (n - ST_FRAME + ST_HOP - 1) / ST_HOP : 0; }      // len(range(0, n - 256, 128))
 
@@ -103,8 +102,8 @@ __global__ __launch_bounds__(256) void stoi_energies_kernel(const float* __restr
 // one workgroup per row: cnt[row] = {n_kept, non-finite flag}, src[row][j] = the j-th kept frame
 __global__ __launch_bounds__(256) void stoi_select_kernel(const double* __restrict__ E, const int* __restrict__ badv, int64_t nf, int64_t nfc,
                                                           int* __restrict__ src, int* __restrict__ cnt) {
-  __shared__ double red_m[4];
-  __shared__ int red_b[4];
+  __shared__ double red_m[4][1];
+  __shared__ int red_b[4][1];
   __shared__ int wtot[4];
   const int64_t row = blockIdx.x;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -118,26 +117,19 @@ __global__ __launch_bounds__(256) void stoi_select_kernel(const double* __restri
     const double v = Er[k];
     m = v > m ? v : m;                          // never reached with a NaN that matters: a flagged row stops below
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(m, o, 64);
-    m = t > m ? t : m;
-  }
-  const int wave_bad = __ballot(bad != 0) != 0;
-  if (lane == 0) {
-    red_m[wave] = m;
-    red_b[wave] = wave_bad;
-  }
+  const double wm[1] = {wave_max_d(m)};
+  const int wb[1] = {__ballot(bad != 0) != 0};
+  wg_park(red_m, wm, wave, lane);             // two types behind one barrier
+  wg_park(red_b, wb, wave, lane);
   __syncthreads();
-  if (red_b[0] | red_b[1] | red_b[2] | red_b[3]) {
+  if (red_b[0][0] | red_b[1][0] | red_b[2][0] | red_b[3][0]) {
     if (tid == 0) {
       cnt[2 * row] = 0;
       cnt[2 * row + 1] = 1;
     }
     return;
   }
-  m = red_m[0];
-  for (int q = 1; q < 4; ++q) m = red_m[q] > m ? red_m[q] : m;
+  m = wg_col<WG_MAX>(red_m, 0);
   int base = 0;
   for (int64_t k0 = 0; k0 < nf; k0 += 256) {
     const int64_t k = k0 + tid;
@@ -191,19 +183,11 @@ __global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < 9; ++s) {
-    const int half = 1 << s;
-    const int j = t & (half - 1);
-    const int i0 = ((t >> s) << (s + 1)) + j, i1 = i0 + half;
+    int i0, i1, j;
+    fft2_index(t, s, i0, i1, j);
     const double c = tw[2 * (j << (8 - s))], sn = tw[2 * (j << (8 - s)) + 1];
 #pragma unroll
-    for (int sig = 0; sig < 2; ++sig) {
-      const double ur = zr[sig][i0], ui = zi[sig][i0], vr = zr[sig][i1], vi = zi[sig][i1];
-      const double pr = c * vr + sn * vi, pi = c * vi - sn * vr;      // (c - i sn) (vr + i vi)
-      zr[sig][i0] = ur + pr;
-      zi[sig][i0] = ui + pi;
-      zr[sig][i1] = ur - pr;
-      zi[sig][i1] = ui - pi;
-    }
+    for (int sig = 0; sig < 2; ++sig) fft2_rotate_add(zr[sig], zi[sig], i0, i1, c, sn);
     __syncthreads();
   }
   if (t < 2 * ST_J) {
@@ -304,7 +288,7 @@ __global__ __launch_bounds__(64) void stoi_finalize_kernel(const double* __restr
   const int lane = threadIdx.x;
   const int n_kept = cnt[2 * row];
   const int nseg = n_kept - 1 >= ST_N ? n_kept - ST_N : 0;     // M - 29 segments of M = n_kept - 1 frames; a flagged row has n_kept = 0
-  double d = st_nan(), e = st_nan();
+  double d = nan_d(), e = nan_d();
   if (nseg > 0) {
     d = wave_strided_sum_d(part + row * scap * 2, nseg, 2, lane) / (double)(ST_J * (int64_t)nseg);
     e = wave_strided_sum_d(part + row * scap * 2 + 1, nseg, 2, lane) / (double)nseg;
@@ -330,16 +314,11 @@ extern "C" int64_t maavss_stoi_ws_bytes(int64_t rows, int64_t n) {
 
 extern "C" int maavss_stoi(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t rows, int64_t n, double* out,
                            void* ws, int64_t ws_bytes, void* stream) {
-  MAAVSS_CHECK_ARG(est && ref && out && ws, "stoi: null pointer");
+  if (int rc = metric_rows_check("stoi", est, est_stride, ref, ref_stride, rows, out, ws)) return rc;
   MAAVSS_CHECK_ARG(rows >= 1 && n >= 1, "stoi: bad sizes (rows %lld, n %lld)", (long long)rows, (long long)n);
   MAAVSS_CHECK_ARG(n < (int64_t)1 << 31, "stoi: n = %lld is beyond the kernels' index range (n < 2^31)", (long long)n);
   MAAVSS_CHECK_ARG(st_sizes_ok(rows, n), "stoi: %lld rows of %lld frames are more workgroups than one launch takes", (long long)rows,
                    (long long)st_frames(n));
-  MAAVSS_CHECK_ARG(rows == 1 || (est_stride >= 0 && ref_stride >= 0 && est_stride < (int64_t)1 << 40 && ref_stride < (int64_t)1 << 40),
-                   "stoi: row strides %lld, %lld: rows would not be addressable (strides are >= 0; rows may overlap)", (long long)est_stride,
-                   (long long)ref_stride);
-  MAAVSS_CHECK_ARG((((uintptr_t)est | (uintptr_t)ref) & 3) == 0, "stoi: est and ref must be 4-byte aligned");
-  MAAVSS_CHECK_ARG((((uintptr_t)out | (uintptr_t)ws) & 7) == 0, "stoi: out and workspace must be 8-byte aligned");
   const st_plan p = st_make_plan(rows, n);
   MAAVSS_CHECK_ARG(ws_bytes >= p.bytes, "stoi: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)p.bytes);
   hipStream_t st = (hipStream_t)stream;

@@ -10,6 +10,7 @@
 // No floating-point atomic anywhere: every output has the same bits in every run.  HBM-bound: 4 bytes read per element per pass,
 // one f64 FMA per element in pass 1.
 #include "common.h"
+#include "metric_f64.h"
 
 #define TS_CH 16384          // chunk length in elements (64 KB: 64 elements per thread of a 256-thread workgroup)
 #define TS_MAX_BINS 1024
@@ -20,8 +21,6 @@ struct ts_partial {
   int n_nan, n_pinf, n_ninf, pad;
 };
 static_assert(sizeof(ts_partial) == 32, "workspace layout of include/maavss.h");
-
-__device__ __forceinline__ bool ts_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // Per-lane running statistics: four independent f64 chains for the sum (the FMA's latency), one chain for the rest.
 struct ts_acc {
@@ -206,16 +205,16 @@ __global__ __launch_bounds__(256) void tensor_stats_hist_kernel(const float* __r
     const int len4 = len >> 2;
     for (int i = tid; i < len4; i += 256) {
       const float4 v = reinterpret_cast<const float4*>(x)[i];
-      if (ts_finite(v.x)) atomicAdd(&h[ts_bin(v.x, lo, width, fbins, bins)], 1);
-      if (ts_finite(v.y)) atomicAdd(&h[ts_bin(v.y, lo, width, fbins, bins)], 1);
-      if (ts_finite(v.z)) atomicAdd(&h[ts_bin(v.z, lo, width, fbins, bins)], 1);
-      if (ts_finite(v.w)) atomicAdd(&h[ts_bin(v.w, lo, width, fbins, bins)], 1);
+      if (!f32_nonfinite(v.x)) atomicAdd(&h[ts_bin(v.x, lo, width, fbins, bins)], 1);
+      if (!f32_nonfinite(v.y)) atomicAdd(&h[ts_bin(v.y, lo, width, fbins, bins)], 1);
+      if (!f32_nonfinite(v.z)) atomicAdd(&h[ts_bin(v.z, lo, width, fbins, bins)], 1);
+      if (!f32_nonfinite(v.w)) atomicAdd(&h[ts_bin(v.w, lo, width, fbins, bins)], 1);
     }
     const int i = (len4 << 2) + tid;
-    if (i < len && ts_finite(x[i])) atomicAdd(&h[ts_bin(x[i], lo, width, fbins, bins)], 1);
+    if (i < len && !f32_nonfinite(x[i])) atomicAdd(&h[ts_bin(x[i], lo, width, fbins, bins)], 1);
   } else {
     for (int i = tid; i < len; i += 256)
-      if (ts_finite(x[i])) atomicAdd(&h[ts_bin(x[i], lo, width, fbins, bins)], 1);
+      if (!f32_nonfinite(x[i])) atomicAdd(&h[ts_bin(x[i], lo, width, fbins, bins)], 1);
   }
   __syncthreads();
   for (int b = tid; b < bins; b += 256)

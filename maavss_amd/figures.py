@@ -8,7 +8,7 @@ import os
 
 import torch
 
-from ._lib import call, ptr, query, require_cuda, stream_ptr
+from ._lib import call, ptr, query, require_cuda, stream_ptr, wave_rows
 
 IMAGE_KEYS = ("stft", "input_mag", "input_phase", "output_mag", "output_phase", "attention_frames")
 _DTYPES = {torch.float32: 0, torch.float64: 1}
@@ -75,23 +75,12 @@ def viridis_image(x, vmin=None, vmax=None, *, transpose=False, flip_rows=False, 
     return res[0] if single else res
 
 
-def _rows(t, what):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (1, 2):
-        raise ValueError(f"{what} must be a float32 tensor [L] or [B, L], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
-    t = t[None] if t.dim() == 1 else t
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what} is empty: {tuple(t.shape)}")
-    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < 0:
-        t = t.contiguous()
-    return t
-
-
 def specgram_planes(wave, nfft=256, noverlap=128):
     """wave: f32 cuda [L] or [B, L], samples contiguous, any row stride >= 0 (rows may overlap) and any 4-byte-aligned offset
     -> (mag_db, phase), both f64 [B, nfft / 2 + 1, n]: the arrays Axes.specgram(x, mode='magnitude') and (mode='phase') hand to imshow
     with matplotlib's other defaults (Hann window, no detrending, one-sided, dB, np.unwrap along frequency, row 0 the Nyquist bin).
     nfft: a power of two in 32 .. 1024; 0 <= noverlap < nfft."""
-    wave = _rows(wave, "wave")
+    wave = wave_rows(wave, "wave")
     for v, what in ((nfft, "nfft"), (noverlap, "noverlap")):
         if isinstance(v, bool) or not isinstance(v, int):
             raise ValueError(f"{what} must be an integer, got {v!r}")

@@ -18,9 +18,11 @@ Definitions (include/maavss.h states them next to the entry points; tests/qualit
   to [-10, 35] dB.  No epsilon: est == ref gives +inf, a silent reference NaN, a non-finite sample makes its row NaN.
 Nothing here synchronises with the host before `Validator.result()`.
 """
+from collections import namedtuple
+
 import torch
 
-from ._lib import MaavssError, call, ptr, query, require_cuda, stream_ptr, workspace
+from ._lib import MaavssError, call, column_dict, ptr, query, require_cuda, require_same_shape, stream_ptr, wave_rows, workspace
 from .bss import BSS_COLUMNS, BSS_DB, BSS_MAX_FILTER, bss_eval_metrics
 from .spectral_loss import SpectralLoss
 from .stoi import stoi_metrics
@@ -49,24 +51,12 @@ def plan_wave_chunks(length, seg_len, ch):
     return [(a, min(cl, length - a)) for a in range(0, length, cl)]
 
 
-def _rows(t, what):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (1, 2):
-        raise ValueError(f"{what} must be a float32 tensor [L] or [B, L], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
-    t = t[None] if t.dim() == 1 else t
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what} is empty: {tuple(t.shape)}")
-    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < 0:
-        t = t.contiguous()
-    return t
-
-
 def wave_metrics(est, ref, seg_len=256):
     """est, ref: f32 cuda [L] or [B, L], samples contiguous, any row stride >= 0 (rows may overlap) and any 4-byte-aligned offset -- a slice
     `clean[start:start + n]` is taken as it is.  -> dict of device f64 tensors [B]: sxx, syy, sxy, see, srr, snr_db, si_sdr_db, seg_snr_db,
     n_frames, and "raw" [B, 9], the one buffer they are columns of.  Only enqueues launches on the current stream."""
-    est, ref = _rows(est, "est"), _rows(ref, "ref")
-    if est.shape != ref.shape:
-        raise ValueError(f"est {tuple(est.shape)} and ref {tuple(ref.shape)} differ in shape")
+    est, ref = wave_rows(est, "est"), wave_rows(ref, "ref")
+    require_same_shape(est, ref)
     ch = wave_chunk()
     if not 1 <= int(seg_len) <= ch:
         raise ValueError(f"seg_len must be in 1..{ch}, got {seg_len}")
@@ -76,9 +66,7 @@ def wave_metrics(est, ref, seg_len=256):
     nbytes = int(query("maavss_wave_metrics_ws_bytes", b, n, int(seg_len)))
     ws = workspace(nbytes, est.device)
     call("maavss_wave_metrics", ptr(est), est.stride(0), ptr(ref), ref.stride(0), b, n, int(seg_len), ptr(out), ptr(ws), nbytes, stream_ptr())
-    res = {k: out[:, i] for i, k in enumerate(WAVE_COLUMNS)}
-    res["raw"] = out
-    return res
+    return column_dict(out, WAVE_COLUMNS)
 
 
 def spectrum_metrics(pred, tgt, lsd_floor=1e-10):
@@ -130,6 +118,24 @@ _BSS_LEN = 5 * len(BSS_DB) * len(_GROUPS)
 _BSS0 = BSS_COLUMNS.index("sdr_db")
 # the fourth accumulator, only with audio_loss: [S_mag, S_cplx, elements] of the spectral loss over the model's audio outputs
 _SPEC_LEN = 3
+_COUNTS = ("n_finite", "n_posinf", "n_neginf", "n_nan")
+
+# What differs between the families of per-clip metrics (everything else add_waves, result() and the buffer's layout do once for all):
+#   names    the columns accumulated, 15 numbers each (five per group)
+#   attr     the Validator attribute that views the family's part of the buffer (the first family's is the tail of `.acc`)
+#   metric   (validator, x, ref, others) -> the raw [B, cols] tensor of x against ref;  col0: its first accumulated column
+#   counts   which of _COUNTS result() reports (a score that is a correlation is never infinite)
+#   clips    the family that counts the clips: result() takes n_clips from its est group and leaves out a noisy_ / _improvement key
+#            nothing was added to; the others always report all their keys
+#   enabled  validator -> bool
+_Family = namedtuple("_Family", "names attr metric col0 counts clips enabled")
+_FAMILIES = (
+    _Family(WAVE_DB, None, lambda v, x, ref, oth: wave_metrics(x, ref, v.seg_len), _DB0, _COUNTS, True, lambda v: True),
+    _Family(_INTEL, "acc_intel", lambda v, x, ref, oth: stoi_metrics(x, ref, v.intelligibility_sr), 0, ("n_finite", "n_nan"), False,
+            lambda v: v.intelligibility_sr is not None),
+    _Family(BSS_DB, "acc_bss", lambda v, x, ref, oth: bss_eval_metrics(x, ref, oth, v.bss_filter), _BSS0, _COUNTS, False,
+            lambda v: v.bss_filter is not None),
+)
 
 
 class Validator:
@@ -190,29 +196,33 @@ class Validator:
         if self._buf is not None:
             self._buf.zero_()
 
+    def _layout(self):
+        """([(family, its offset in _buf)] of the enabled families, the length of _buf): the sums, the families in table order, then
+        the spectral tail"""
+        o, fams = 2 * len(_SUMS), []
+        for f in _FAMILIES:
+            if f.enabled(self):
+                fams.append((f, o))
+                o += 5 * len(f.names) * len(_GROUPS)
+        return fams, o + (0 if self.audio_loss is None else _SPEC_LEN)
+
     def _acc(self, dev):
         if self.acc is None:
-            extra = 0 if self.intelligibility_sr is None else _INTEL_LEN
-            self._buf = torch.zeros(self._buf_len(), dtype=torch.float64, device=dev)
+            fams, n = self._layout()
+            self._buf = torch.zeros(n, dtype=torch.float64, device=dev)
             self.acc = self._buf[:_ACC_LEN]
-            if extra:
-                self.acc_intel = self._buf[_ACC_LEN:_ACC_LEN + extra]
-            if self.bss_filter is not None:
-                self.acc_bss = self._buf[_ACC_LEN + extra:_ACC_LEN + extra + _BSS_LEN]
+            for f, o in fams[1:]:
+                setattr(self, f.attr, self._buf[o:o + 5 * len(f.names) * len(_GROUPS)])
             if self.audio_loss is not None:
-                self.acc_spec = self._buf[self._buf_len() - _SPEC_LEN:]
+                self.acc_spec = self._buf[n - _SPEC_LEN:]
         return self.acc
 
     def _buf_len(self):
-        return (_ACC_LEN + (0 if self.intelligibility_sr is None else _INTEL_LEN) + (0 if self.bss_filter is None else _BSS_LEN)
-                + (0 if self.audio_loss is None else _SPEC_LEN))
+        return self._layout()[1]
 
-    def _slot(self, kind, group=None):
-        if group is None:
-            o = 2 * _SUMS.index(kind)
-            return self.acc[o:o + 2]
-        o = 2 * len(_SUMS) + 5 * len(WAVE_DB) * _GROUPS.index(group)
-        return self.acc[o:o + 5 * len(WAVE_DB)]
+    def _slot(self, kind):
+        o = 2 * _SUMS.index(kind)
+        return self.acc[o:o + 2]
 
     def _check_eval(self):
         if self.model.training:
@@ -254,35 +264,19 @@ class Validator:
         [B, K, L], the other sources of each row's mixture) is read only with bss_filter."""
         if others is not None and self.bss_filter is None:
             raise ValueError("others is given but this Validator was built without bss_filter")
-        m = wave_metrics(est, ref, self.seg_len)["raw"]
-        self._acc(m.device)
-        st = stream_ptr()
-        b, cols, k = m.shape[0], m.shape[1], len(WAVE_DB)
-        call("maavss_metric_add_classes", ptr(m[:, _DB0:]), None, b, cols, k, ptr(self._slot(None, "est")), st)
-        if noisy is not None:
-            mn = wave_metrics(noisy, ref, self.seg_len)["raw"]
-            if mn.shape != m.shape:
-                raise ValueError("noisy must have the shape of est")
-            call("maavss_metric_add_classes", ptr(mn[:, _DB0:]), None, b, cols, k, ptr(self._slot(None, "noisy")), st)
-            call("maavss_metric_add_classes", ptr(m[:, _DB0:]), ptr(mn[:, _DB0:]), b, cols, k, ptr(self._slot(None, "gain")), st)
-        if self.intelligibility_sr is not None:
-            s = stoi_metrics(est, ref, self.intelligibility_sr)["raw"]
-            cols, k = s.shape[1], len(_INTEL)
-            slot = {g: self.acc_intel[5 * k * i:5 * k * (i + 1)] for i, g in enumerate(_GROUPS)}
-            call("maavss_metric_add_classes", ptr(s), None, b, cols, k, ptr(slot["est"]), st)
+        for f, o in self._layout()[0]:
+            m = f.metric(self, est, ref, others)["raw"]
+            self._acc(m.device)
+            st = stream_ptr()
+            (b, cols), k = m.shape, len(f.names)
+            slot = [self._buf[o + 5 * k * i:] for i in range(len(_GROUPS))]          # est, noisy, gain
+            call("maavss_metric_add_classes", ptr(m[:, f.col0:]), None, b, cols, k, ptr(slot[0]), st)
             if noisy is not None:
-                sn = stoi_metrics(noisy, ref, self.intelligibility_sr)["raw"]
-                call("maavss_metric_add_classes", ptr(sn), None, b, cols, k, ptr(slot["noisy"]), st)
-                call("maavss_metric_add_classes", ptr(s), ptr(sn), b, cols, k, ptr(slot["gain"]), st)
-        if self.bss_filter is not None:
-            s = bss_eval_metrics(est, ref, others, self.bss_filter)["raw"]
-            cols, k = s.shape[1], len(BSS_DB)
-            slot = {g: self.acc_bss[5 * k * i:5 * k * (i + 1)] for i, g in enumerate(_GROUPS)}
-            call("maavss_metric_add_classes", ptr(s[:, _BSS0:]), None, b, cols, k, ptr(slot["est"]), st)
-            if noisy is not None:
-                sn = bss_eval_metrics(noisy, ref, others, self.bss_filter)["raw"]
-                call("maavss_metric_add_classes", ptr(sn[:, _BSS0:]), None, b, cols, k, ptr(slot["noisy"]), st)
-                call("maavss_metric_add_classes", ptr(s[:, _BSS0:]), ptr(sn[:, _BSS0:]), b, cols, k, ptr(slot["gain"]), st)
+                mn = f.metric(self, noisy, ref, others)["raw"]
+                if mn.shape != m.shape:
+                    raise ValueError("noisy must have the shape of est")
+                call("maavss_metric_add_classes", ptr(mn[:, f.col0:]), None, b, cols, k, ptr(slot[1]), st)
+                call("maavss_metric_add_classes", ptr(m[:, f.col0:]), ptr(mn[:, f.col0:]), b, cols, k, ptr(slot[2]), st)
 
     def add_recording(self, enhancer, noisy, clean, frames=None, attn=None, others=None):
         """Enhance `noisy` [L] with `enhancer(noisy, frames= | attn=)` -> (wave, start) and measure the estimate and the noisy input against
@@ -328,37 +322,22 @@ class Validator:
 
         out = {"val_loss_stft": ratio(h[0], h[1]), "lsd_db": ratio(h[2], h[3]), "val_loss_attn": ratio(h[4], h[5]), "n_windows": int(h[3])}
         out["val_loss"] = out["val_loss_stft"] + self.loss_coeff * out["val_loss_attn"]
-        o = 2 * len(_SUMS)
-        for group in _GROUPS:
-            for name in WAVE_DB:
-                s, nf, npos, nneg, nnan = h[o:o + 5]
-                o += 5
-                total = int(nf + npos + nneg + nnan)
-                if group == "est":
-                    out["n_clips"] = total
-                elif total == 0:
-                    continue
-                key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
-                out[key] = ratio(s, nf)
-                out.update({f"{key}_n_finite": int(nf), f"{key}_n_posinf": int(npos), f"{key}_n_neginf": int(nneg), f"{key}_n_nan": int(nnan)})
-        if self.intelligibility_sr is not None:
+        for f, o in self._layout()[0]:
             for group in _GROUPS:
-                for name in _INTEL:
-                    s, nf, _, _, nnan = h[o:o + 5]          # a score is a correlation: never infinite
-                    o += 5
-                    key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
-                    out[key] = ratio(s, nf)
-                    out.update({f"{key}_n_finite": int(nf), f"{key}_n_nan": int(nnan)})
-        if self.bss_filter is not None:
-            for group in _GROUPS:
-                for name in BSS_DB:
+                for name in f.names:
                     s, nf, npos, nneg, nnan = h[o:o + 5]
                     o += 5
+                    if f.clips:
+                        total = int(nf + npos + nneg + nnan)
+                        if group == "est":
+                            out["n_clips"] = total
+                        elif total == 0:
+                            continue
                     key = {"est": name, "noisy": "noisy_" + name, "gain": name + "_improvement"}[group]
                     out[key] = ratio(s, nf)
-                    out.update({f"{key}_n_finite": int(nf), f"{key}_n_posinf": int(npos), f"{key}_n_neginf": int(nneg), f"{key}_n_nan": int(nnan)})
+                    out.update({f"{key}_{c}": int(n) for c, n in zip(_COUNTS, (nf, npos, nneg, nnan)) if c in f.counts})
         if self.audio_loss is not None:
-            s_mag, s_cplx, n = h[o:o + _SPEC_LEN]
+            s_mag, s_cplx, n = h[-_SPEC_LEN:]
             out["val_loss_spectral_mag"], out["val_loss_spectral_cplx"] = ratio(s_mag, n), ratio(s_cplx, n)
             out["val_loss_spectral"] = ratio((1.0 - self.audio_loss.mix) * s_mag + self.audio_loss.mix * s_cplx, n)
             out["val_objective"] = out["val_loss_spectral"] + self.loss_coeff * out["val_loss_attn"]

@@ -4,23 +4,12 @@ floating-point atomics).  include/maavss.h states the definition next to maavss_
 Nothing here waits for the device: `Validator(intelligibility_sr=...)` accumulates the scores, `Validator.result()` copies them."""
 import torch
 
-from ._lib import call, ptr, query, require_cuda, stream_ptr, workspace
+from ._lib import call, column_dict, ptr, query, require_cuda, require_same_shape, stream_ptr, wave_rows, workspace
 from .audio_transform import AudioTransform
 
 STOI_SR = 10000                      # the rate the measure is defined at
 STOI_COLUMNS = ("stoi", "estoi", "n_kept", "n_segments")
 _resample = AudioTransform(STOI_SR)  # holds no device memory until a rate other than 10 kHz is asked for; its tap tables are kept per rate
-
-
-def _rows(t, what):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (1, 2):
-        raise ValueError(f"{what} must be a float32 tensor [L] or [B, L], got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
-    t = t[None] if t.dim() == 1 else t
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what} is empty: {tuple(t.shape)}")
-    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < 0:
-        t = t.contiguous()
-    return t
 
 
 def stoi_metrics(est, ref, sr=STOI_SR):
@@ -29,9 +18,8 @@ def stoi_metrics(est, ref, sr=STOI_SR):
     and n_segments (384 ms segments scored), and "raw" [B, 4], the one buffer they are columns of.  A row without a segment (shorter than
     31 kept frames, a silent reference) or with a non-finite sample scores NaN with n_segments = 0.  sr != 10000 sends both through
     AudioTransform(10000) first, on the device.  Only enqueues launches on the current stream."""
-    est, ref = _rows(est, "est"), _rows(ref, "ref")
-    if est.shape != ref.shape:
-        raise ValueError(f"est {tuple(est.shape)} and ref {tuple(ref.shape)} differ in shape")
+    est, ref = wave_rows(est, "est"), wave_rows(ref, "ref")
+    require_same_shape(est, ref)
     if isinstance(sr, bool) or not isinstance(sr, int) or sr < 1:
         raise ValueError(f"sr must be a positive integer (samples per second), got {sr!r}")
     if sr != STOI_SR:
@@ -46,6 +34,4 @@ def stoi_metrics(est, ref, sr=STOI_SR):
     out = torch.empty(b, len(STOI_COLUMNS), dtype=torch.float64, device=est.device)
     ws = workspace(nbytes, est.device)
     call("maavss_stoi", ptr(est), est.stride(0), ptr(ref), ref.stride(0), b, n, ptr(out), ptr(ws), nbytes, stream_ptr())
-    res = {k: out[:, i] for i, k in enumerate(STOI_COLUMNS)}
-    res["raw"] = out
-    return res
+    return column_dict(out, STOI_COLUMNS)

@@ -1,8 +1,11 @@
 """CPU-only part of the quality metrics (maavss_amd/quality.py, csrc/quality_metrics.hip): known answers of the float64 twin, the chunk
 planner, exports and the pinned ABI version, the argument checks of the new entry points (every call below fails before any launch)
-and the Validator's refusals."""
+the Validator's refusals, result() on a known buffer and the launches add_waves enqueues."""
 import inspect
+import itertools
+import json
 import math
+import os
 import re
 import types
 
@@ -226,3 +229,97 @@ def test_nothing_in_quality_py_waits_for_the_device_before_result():
     assert pat.search(body), "result() makes the one copy"
     assert len(re.findall(r"\.cpu\(", body)) == 1
     assert not pat.search(rest), pat.search(rest)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "validator_result.json")
+OPTIONS = list(itertools.product((False, True), repeat=3))         # intelligibility_sr, bss_filter, audio_loss: on or off
+
+
+def _validator(intel, bss, loss):
+    import maavss_amd
+    return maavss_amd.Validator(types.SimpleNamespace(training=False), loss_coeff=0.5, intelligibility_sr=16000 if intel else None,
+                                bss_filter=32 if bss else None, audio_loss=maavss_amd.SpectralLoss(mix=0.25) if loss else None)
+
+
+def known_buffer_results():
+    """{"<intel><bss><loss>/<fill>": [[key, value], ...]}: result() of every option combination on a CPU buffer of 1, 2, ..., n and of
+    zeros, in the order of its keys, a NaN as None.  tests/golden/validator_result.json holds what this returned at the commit
+    before the Validator's family table (run there with that tree's package on the path); no library and no device is needed."""
+    res = {}
+    for opt in OPTIONS:
+        for fill in ("arange", "zeros"):
+            val = _validator(*opt)
+            n = val._buf_len()
+            val._buf = torch.arange(1, n + 1, dtype=torch.float64) if fill == "arange" else torch.zeros(n, dtype=torch.float64)
+            out = val.result()
+            res["%d%d%d/%s" % (*opt, fill)] = [[k, None if isinstance(v, float) and math.isnan(v) else v] for k, v in out.items()]
+    return res
+
+
+def test_result_of_a_known_buffer_is_what_it_was_before_the_family_table():
+    want = json.load(open(GOLDEN))
+    got = known_buffer_results()
+    assert list(got) == list(want) and len(want) == 16
+    for case in want:
+        assert [k for k, _ in got[case]] == [k for k, _ in want[case]], case                       # the keys, in order
+        for (k, a), (_, b) in zip(got[case], want[case]):
+            assert type(a) is type(b) and a == b, (case, k, a, b)                                   # None stands for NaN; an int stays an int
+    assert len(want["111/arange"]) == 118 and len(got["111/arange"]) == 118
+
+
+# per family: the width of its raw tensor, the first accumulated column, the number of accumulated columns
+FAMILY_SHAPE = {"wave": (9, 5, 3), "stoi": (4, 0, 2), "bss": (10, 5, 3)}
+
+
+@pytest.mark.parametrize("with_noisy", (False, True))
+@pytest.mark.parametrize("intel,bss,loss", OPTIONS)
+def test_add_waves_enqueues_the_same_launches_in_the_same_order(monkeypatch, intel, bss, loss, with_noisy):
+    import maavss_amd.quality as q
+    B = 3
+    est, ref, noisy, others = (torch.zeros(B, 64) for _ in range(4))
+    log, made = [], {}
+
+    def metric(family):
+        def stub(x, r, *extra):
+            assert r is ref and extra == {"wave": (256,), "stoi": (16000,), "bss": (others, 32)}[family]
+            who = "est" if x is est else "noisy"
+            assert x is (est if who == "est" else noisy)
+            log.append(("metric", family, who))
+            made[family, who] = torch.zeros(B, FAMILY_SHAPE[family][0], dtype=torch.float64)
+            return {"raw": made[family, who]}
+        return stub
+
+    def where(p):
+        """the tensor a pointer lies in, and its offset in f64 elements"""
+        if p is None:
+            return None
+        for tag, t in list(made.items()) + [("acc", val._buf)]:
+            if t.data_ptr() <= p < t.data_ptr() + 8 * t.numel():
+                return tag, (p - t.data_ptr()) // 8
+        raise AssertionError("a pointer into no known tensor")
+
+    def call(name, vals, minus, rows, stride, cols, acc, stream):
+        assert stream == 77
+        log.append((name, where(vals), where(minus), rows, stride, cols, where(acc)))
+
+    monkeypatch.setattr(q, "call", call)
+    monkeypatch.setattr(q, "stream_ptr", lambda: 77)
+    for family, name in (("wave", "wave_metrics"), ("stoi", "stoi_metrics"), ("bss", "bss_eval_metrics")):
+        monkeypatch.setattr(q, name, metric(family))
+    val = _validator(intel, bss, loss)
+    val.add_waves(est, ref, noisy=noisy if with_noisy else None, others=others if bss else None)
+    assert val._buf.shape == (51 + 30 * intel + 45 * bss + 3 * loss,) and val.acc.shape == (51,)
+
+    # the first accumulator slot of each enabled family: after the six sums, then in the order wave, intelligibility, BSS
+    first = {"wave": 6, "stoi": 51, "bss": 81 if intel else 51}
+    want = []
+    for family in ["wave"] + ["stoi"] * intel + ["bss"] * bss:
+        width, col0, k = FAMILY_SHAPE[family]
+        add = "maavss_metric_add_classes"
+        want += [("metric", family, "est"),
+                 (add, ((family, "est"), col0), None, B, width, k, ("acc", first[family]))]
+        if with_noisy:
+            want += [("metric", family, "noisy"),
+                     (add, ((family, "noisy"), col0), None, B, width, k, ("acc", first[family] + 5 * k)),
+                     (add, ((family, "est"), col0), ((family, "noisy"), col0), B, width, k, ("acc", first[family] + 10 * k))]
+    assert log == want
