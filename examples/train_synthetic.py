@@ -10,6 +10,9 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --raw_video 360x640 [--autocontrast]   # decoded uint8 clips through VideoTransform first
     python examples/train_synthetic.py --raw_audio [--compress_audio]         # 44.1 kHz stereo int16 clips through AudioTransform first
     python examples/train_synthetic.py --mix 2 --mix_snr 0 10                 # mix-and-separate: every clip + 2 others of the batch at 0..10 dB
+    python examples/train_synthetic.py --reverb 16 [--reverb_target dry]      # every clip in one of 16 synthetic rooms, new rooms every epoch
+                                                                              # (maavss_amd.Reverb; with --bank a clip hears its recording's
+                                                                              # past); dry: the target stays the dry clip (dereverberation)
     python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
     python examples/train_synthetic.py --val 2                                # every 2 steps: held-out loss and LSD, a checkpoint on improvement
     python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
@@ -60,6 +63,10 @@ def main():
     ap.add_argument("--mix", type=int, default=0, metavar="K",
                     help="mix-and-separate: add K other clips of the batch (1..4) to every clip's input; each clip is its own set of sinusoids")
     ap.add_argument("--mix_snr", type=float, nargs=2, default=(0.0, 10.0), metavar=("LO", "HI"), help="with --mix: signal-to-interferer range in dB")
+    ap.add_argument("--reverb", type=int, default=0, metavar="N",
+                    help="convolve every clip with one of N synthetic room responses of 0.5 s (maavss_amd.Reverb), N new rooms every epoch")
+    ap.add_argument("--reverb_target", choices=("wet", "dry"), default="wet",
+                    help="with --reverb: the target is the reverberant clip (wet) or the dry one (dry: not together with --mix)")
     ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM",
                     help="clip the global gradient norm (clip_grad_norm_'s rule, on the device: TrainStep(max_grad_norm=...))")
     ap.add_argument("--watch", type=int, default=0, metavar="N",
@@ -97,6 +104,8 @@ def main():
         ap.error("--select chooses among the clips of a bank: it goes with --bank")
     if a.bank and (a.raw_video or a.raw_audio or a.overfit):
         ap.error("--bank holds transformed frames' maps and 16 kHz audio: it does not go with --raw_video, --raw_audio or --overfit")
+    if a.reverb and a.reverb_target == "dry" and a.mix:
+        ap.error("--reverb_target dry does not go with --mix: the target of a reverberant mixture is not built")
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
     t_total = nf + ns - 1                                      # frames per clip so that num_seq windows fit (av_dataset.py:251-278)
@@ -125,9 +134,12 @@ def main():
         audio_transform = maavss_amd.AudioTransform(16000, compress_audio=a.compress_audio)
         raw_length = audio_transform.input_length(length, raw_sr)      # the fewest 44.1 kHz samples that give `length` at 16 kHz
     mixer = maavss_amd.Mixer(stft, a.mix, tuple(a.mix_snr)) if a.mix else None
+    reverb = maavss_amd.Reverb(8000, rt60=(0.2, 0.5), device=dev) if a.reverb else None
+    if reverb is not None:
+        reverb.make_rirs(a.reverb, seed=0)                       # epoch 0's rooms; submit() below makes the later ones
     if not a.bank:
         pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform, audio_transform=audio_transform,
-                                       audio_length=length if a.raw_audio else None, mixer=mixer)
+                                       audio_length=length if a.raw_audio else None, mixer=mixer, reverb=reverb, reverb_target=a.reverb_target)
 
     g = torch.Generator().manual_seed(0)
 
@@ -181,7 +193,7 @@ def main():
             ap.error(f"--bank {a.bank} holds {n_train} clips, fewer than one batch of {b}")
         print(f"bank: {len(bank)} clips of {n_rec} recordings, {bank.maps.numel() * bank.maps.element_size() / 1e6:.2f} MB of maps "
               f"({a.bank_storage}), {bank.audio.numel() * 4 / 1e6:.2f} MB of audio", flush=True)
-        pipe = maavss_amd.ClipPipeline(None, stft, clip_frames=t_total, bank=bank, mixer=mixer)
+        pipe = maavss_amd.ClipPipeline(None, stft, clip_frames=t_total, bank=bank, mixer=mixer, reverb=reverb, reverb_target=a.reverb_target)
         g_order, order = torch.Generator().manual_seed(0), []
         if a.select:
             # one pass over the bank on the device (ClipBank.activity), the thresholds there too, one copy of a byte per clip back
@@ -204,6 +216,19 @@ def main():
                 while len(order) < b:                                    # the next epoch's permutation of the training clips
                     order.extend(torch.randperm(n_train, generator=g_order).tolist())
                 pipe.submit_clips([order.pop(0) for _ in range(b)], seed=seed)
+
+    if reverb is not None:
+        # an epoch: the sampler's, or one pass over the bank's training clips, or (clips drawn on the fly) 8 steps
+        epoch_steps = len(sampler) if a.select else (max(1, n_train // b) if a.bank else 8)
+        submit_clips = submit
+
+        def submit(seed):
+            if seed and seed % epoch_steps == 0:
+                # the side stream may still read the old table: keep its memory until that work is done.  The new one is written on
+                # this stream in front of the submit, which the side stream waits for
+                reverb.rirs.record_stream(pipe.side)
+                reverb.make_rirs(a.reverb, seed=seed // epoch_steps)
+            submit_clips(seed)
 
     held_out = validator = val_dir = None
     if a.val:

@@ -825,6 +825,48 @@ int maavss_specgram(const float* wave, int64_t stride, int64_t rows, int64_t L, 
 int maavss_filmstrip(const float* y_attn, const float* yh_attn, const float* video, int T, int H, int W, float* maxes, void* out,
                      void* stream);
 
+/* ---- EXTENSION: reverberation (maavss_amd.Reverb) ---------------------------------------------------------------------------------
+ * The reference's only corruption is white noise on the STFT coefficients (av_dataset.py:217-220) and the mixer adds dry clips; this
+ * changes the acoustics of a source: a synthetic room response, and its convolution with audio whose past is read from where it lies
+ * (a clip bank's recording), not assumed silent.  tests/reverb_twin.py restates both definitions in float64.  No entry point allocates,
+ * synchronises or uses an atomic; two runs give identical bytes.  Additive symbols (nothing existing changed meaning).
+ *
+ * Room response of K taps (1 <= K <= maavss_rir_max_taps() = 32768), row r of params f64 [n_rirs][3] = (lam, D, k0):
+ * lam = ln(1000) / (rt60 * sr) (60 dB of amplitude decay per rt60), D = 10^(drr_db / 10), both formed by the caller in f64; k0 the
+ * predelay in samples, read as 1 below 1 (or NaN) and as K above K.
+ *   h[0] = 1 (the direct path at lag 0: wet = dry + tail, aligned with the dry signal);  h[k] = 0.0 for 1 <= k < k0;
+ *   h[k] = f32(s * t_k) for k0 <= k < K,  t_k = (double)g[k] * exp((-lam) * (double)k),  s = sqrt(1.0 / (D * E)),  E = sum t_k^2,
+ * every operation in f64 and rounded on its own (t_k^2 is rounded before it is added), each tap rounded once to f32, so that
+ * 10 log10(1 / sum_{k >= k0} (s t_k)^2) = drr_db over the truncated tail as stored.  E in ONE order: "thread" t of 256 takes the quads
+ * (taps 4 q .. 4 q + 3) q = t, t + 256, ... in index order and adds each quad's squares in tap order, from +0.0 (a tap in front of k0
+ * adds nothing); the 64 sums of each of the four "waves" (threads 64 w .. 64 w + 63) go through the butterfly v[l] += v[l ^ o],
+ * o = 32, 16, 8, 4, 2, 1; the four results as (w0 + w1) + (w2 + w3).  When E > 0 is false (k0 >= K, silent noise, a NaN) or s = 0,
+ * every tap behind h[0] is +0.0: h = [1, 0, ...].  exp is the device library's (a few ulp): tests/reverb_twin.py derives what that
+ * allows a tap to differ from the twin's.
+ * g: noise[r * ld_noise + k] (f32) when noise is given; otherwise the four taps of quad q of row r are the four deviates of
+ * philox_normal4(seed, idx) in order, idx = 0x52455642 << 32 | (row0 + r) << 13 | q (row0 + n_rirs <= 2^19): a row's bytes depend on
+ * (seed, row0 + r, its parameters, K) only, not on n_rirs or on the launch.  rirs [n_rirs][ld_rir], ld_rir >= K; the padding is not
+ * written.  rirs must not overlap noise.  One launch, one workgroup per row. */
+int maavss_rir_max_taps(void);
+int maavss_rir_synth(const double* params, const float* noise, int64_t ld_noise, uint64_t seed, int64_t row0, int64_t n_rirs, int K,
+                     float* rirs, int64_t ld_rir, void* stream);
+/* out[b * ld_out + n] = f32( sum over k = 0 .. K - 1 with p >= floor[b] of (double)h[k] * (double)src[p] ),  p = start[b] + n - k,
+ * 0 <= n < L, h = rirs + rir_index[b] * ld_rir.  src: one flat f32 buffer of n_src samples; rows start[b] .. start[b] + L - 1 may begin
+ * at any sample and may overlap; the samples floor[b] .. start[b] - 1 are row b's history (floor = start: from zero state).  A term with
+ * p < floor[b] is left out of the sum, not added as a zero, and no tap is skipped for being zero: IEEE decides what an inf or NaN
+ * sample does, and it reaches the K outputs from its own position on and no others.
+ * Every product of two f32 values is exact in f64, so only the order of the additions matters, and it is ONE order: per output, S = 4
+ * partial sums, each from +0.0; tap k goes to partial k mod 4, taps ascending; out = f32((a0 + a1) + (a2 + a3)).  The tiling does not
+ * enter: a row in a batch has the bytes of a call of its own.
+ * start, floor: device int64 [B] (8-byte aligned), rir_index: device int32 [B]; the kernel clamps what it reads from them (start into
+ * [0, n_src - L], floor into [0, start], the index into [0, n_rirs)).  host_*: the same tables in host memory, checked entry by entry
+ * before the launch: start[b] + L > n_src, floor[b] > start[b], a negative entry or an index outside [0, n_rirs) is refused.
+ * 64-bit offsets; 1 <= K <= 32768, L >= 1, ld_out >= L, ld_rir >= K.  out must overlap neither src nor rirs.  One launch: a workgroup
+ * per 1024 consecutive outputs of a row, the taps staged through LDS 1024 at a time. */
+int maavss_reverb(const float* src, int64_t n_src, const int64_t* start, const int64_t* floor, const int64_t* host_start,
+                  const int64_t* host_floor, int64_t B, int64_t L, const float* rirs, int64_t n_rirs, int64_t ld_rir, int K,
+                  const int32_t* rir_index, const int32_t* host_rir_index, float* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .video_transform import VideoTransform  # noqa: F401
 from .audio_transform import AudioTransform  # noqa: F401
 from .enhance import Enhancer  # noqa: F401
 from .mixer import Mixer  # noqa: F401
+from .reverb import Reverb  # noqa: F401
 from .tensor_stats import ModelWatch, TensorStats, plan_chunks  # noqa: F401
 from .quality import Validator, plan_wave_chunks, spectrum_metrics, wave_metrics  # noqa: F401
 from .stoi import stoi_metrics  # noqa: F401

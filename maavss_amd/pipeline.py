@@ -18,13 +18,19 @@ With `mixer` (a Mixer built on the same STFT) the bare STFT call becomes the mix
 With `bank` (a ClipBank) the batches come from attention maps and audio already resident on the device: `submit_clips(indices, seed)`
 cuts them on the side stream (no ViT, no frame or audio transform) in front of the same STFT / mixer call; `video_attention` may
 then be None.
+With `reverb` (a Reverb holding a table of room responses) every clip is convolved with a room on the side stream in front of that
+call: from zero state in submit(), from its recording's past in the bank in submit_clips().  reverb_target="wet": the wet clips take
+the place of the audio, so y is reverberant too and every interferer of a mixture carries its own room; "dry": x is the STFT of the
+wet clips (with its noise), y the STFT of the dry ones -- the network learns to dereverberate.  "dry" with a mixer is not built.
 """
 import torch
+
+from .reverb import bank_floor
 
 
 class ClipPipeline:
     def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None, audio_transform=None,
-                 audio_length=None, mixer=None, bank=None):
+                 audio_length=None, mixer=None, bank=None, reverb=None, reverb_target="wet"):
         self.va, self.stft, self.t = video_attention, stft, clip_frames
         if bank is not None:
             if transform is not None or audio_transform is not None:
@@ -41,6 +47,11 @@ class ClipPipeline:
         if mixer is not None and mixer.stft is not stft:
             raise ValueError("mixer= must be built on the STFT object the pipeline is given")
         self.mixer = mixer
+        if reverb_target not in ("wet", "dry"):
+            raise ValueError(f"reverb_target must be 'wet' or 'dry', got {reverb_target!r}")
+        if reverb is not None and reverb_target == "dry" and mixer is not None:
+            raise ValueError("reverb_target='dry' together with mixer= is not built: the target of a reverberant mixture is left open")
+        self.reverb, self.reverb_target = reverb, reverb_target
         self.depth = depth
         self.finite_check = finite_check
         self.side = torch.cuda.Stream()
@@ -82,7 +93,28 @@ class ClipPipeline:
             snr_db = drawn[1] if snr_db is None else snr_db
         return self.mixer.check(clips, partners, snr_db)
 
-    def submit(self, frames, audio, seed, boxes=None, audio_sr=None, partners=None, snr_db=None):
+    def check_reverb(self, clips, seed, rir_index):
+        """Host-side validation / seeded draw of the rooms (no device work) -> rir_index for the reverb, None without one.  `clips` is
+        the [B, L] tensor the reverb will see or, when it does not exist yet, the pair (B, L)."""
+        if self.reverb is None:
+            if rir_index is not None:
+                raise ValueError("rir_index needs a ClipPipeline built with reverb=")
+            return None
+        return self.reverb.check(clips, rir_index, seed)
+
+    def _encode(self, slot, audio, wet, partners, snr_db, seed):
+        """The STFT / mixer call of one batch on the current (side) stream: `wet` is None without a reverb."""
+        if wet is not None and self.reverb_target == "dry":
+            slot["x"] = self.stft(wet, seed=seed)[0]
+            slot["y"] = self.stft(audio, want_x=False)[1]
+            return
+        audio = audio if wet is None else wet
+        if self.mixer is not None:
+            slot["x"], slot["y"] = self.mixer(audio, partners, snr_db, seed=seed)
+        else:
+            slot["x"], slot["y"] = self.stft(audio, seed=seed)    # replaces (frees) the tensors of two batches ago, after the wait on `consumed`
+
+    def submit(self, frames, audio, seed, boxes=None, audio_sr=None, partners=None, snr_db=None, rir_index=None):
         """Enqueue the extraction of one batch: frames [B*T,3,H,W], audio [B,L] (both resident on the device).  The caller's
         stream must already hold the work that produced them (the side stream waits for it).
         With a transform, frames are the uint8 clips [B*T,H0,W0,3] or [B,T,H0,W0,3] and `boxes` the CPU crop boxes [B,4]; by default
@@ -91,13 +123,17 @@ class ClipPipeline:
         least audio_length samples and are cropped to that.
         With a mixer, `partners` [B,K] int32 and `snr_db` [B] (CPU) choose the mixtures; by default
         mixer.sample(B, torch.Generator().manual_seed(seed)), which is also what mixer(audio, seed=seed) draws: a pipelined and a serial
-        run see the same mixtures."""
+        run see the same mixtures.
+        With a reverb, `rir_index` [B] int32 (CPU) chooses each clip's room in reverb.rirs; by default
+        reverb.sample_index(B, torch.Generator().manual_seed(seed)), which is also what reverb(audio, seed=seed) draws.  The clips
+        (after the audio transform) are convolved from zero state."""
         if self.va is None:
             raise ValueError("submit() needs a ClipPipeline built with a video_attention (a bank-fed one takes submit_clips())")
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
         slot = self.slots[self.head % self.depth]
         raw_audio = self.check_audio(audio, audio_sr)                        # everything is validated before any device work
         partners, snr_db = self.check_mix(audio, raw_audio, seed, partners, snr_db)
+        rir_index = self.check_reverb(audio if raw_audio is None else (raw_audio.shape[0], self.audio_length), seed, rir_index)
         if self.transform is not None:
             raw, _, boxes = self.transform.check(frames, boxes, self.t)
             f, h0, w0, _ = raw.shape
@@ -130,17 +166,16 @@ class ClipPipeline:
                 if slot["audio"] is None or slot["audio"].shape != (nb, self.audio_length):
                     slot["audio"] = torch.empty(nb, self.audio_length, device=audio.device, dtype=torch.float32)
                 audio = self.audio_transform(raw_audio, audio_sr, length=self.audio_length, out=slot["audio"])
-            if self.mixer is not None:
-                slot["x"], slot["y"] = self.mixer(audio, partners, snr_db, seed=seed)
-            else:
-                slot["x"], slot["y"] = self.stft(audio, seed=seed)    # replaces (frees) the tensors of two batches ago, after the wait above
+            wet = None if self.reverb is None else self.reverb(audio, rir_index)
+            self._encode(slot, audio, wet, partners, snr_db, seed)
             slot["ready"].record(self.side)
         self.head += 1
 
-    def submit_clips(self, indices, seed, *, attn_diff=False, partners=None, snr_db=None):
+    def submit_clips(self, indices, seed, *, attn_diff=False, partners=None, snr_db=None, rir_index=None):
         """Enqueue one batch cut from the bank: `indices` as ClipBank.batch takes them (CPU; checked before any device work), `seed`,
         `partners` and `snr_db` as in submit().  On the side stream bank.batch fills the slot's buffers, then the STFT / mixer call and
-        the events are those of submit(); get() / release() do not change."""
+        the events are those of submit(); get() / release() do not change.  With a reverb the wet clips are reverb.bank_clips(bank, indices,
+        rir_index): convolved from bank.audio, each clip with its recording's past."""
         if self.bank is None:
             raise ValueError("submit_clips needs a ClipPipeline built with bank=")
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
@@ -149,6 +184,10 @@ class ClipPipeline:
         starts = bank.check_indices(indices)
         b = starts[0].numel()
         partners, snr_db = self.check_mix((b, bank.clip_samples), None, seed, partners, snr_db)
+        rir_index = self.check_reverb((b, bank.clip_samples), seed, rir_index)
+        if self.reverb is not None:
+            self.reverb.check_bank(bank, b, rir_index, seed)
+            floor = bank_floor(bank, indices)
         f, s = b * self.t, bank.frame_size
         main = torch.cuda.current_stream()
         produced = torch.cuda.Event()
@@ -162,10 +201,8 @@ class ClipPipeline:
             if slot.get("clips") is None or slot["clips"].shape != (b, bank.clip_samples):
                 slot["clips"] = torch.empty(b, bank.clip_samples, device=bank.device, dtype=torch.float32)
             _, audio = bank.cut(*starts, attn_diff=attn_diff, out=(slot["attn"].view(b, 1, self.t, s, s), slot["clips"]))
-            if self.mixer is not None:
-                slot["x"], slot["y"] = self.mixer(audio, partners, snr_db, seed=seed)
-            else:
-                slot["x"], slot["y"] = self.stft(audio, seed=seed)
+            wet = None if self.reverb is None else self.reverb.cut(bank, starts[1], floor, rir_index)
+            self._encode(slot, audio, wet, partners, snr_db, seed)
             slot["ready"].record(self.side)
         self.head += 1
 

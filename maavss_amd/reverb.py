@@ -1,0 +1,227 @@
+"""Reverberation: synthetic room impulse responses and their convolution with clips, the third of the augmentations an enhancement
+data set rests on (additive noise: STFT; interfering sources: Mixer).  The reference has none (av_dataset.py:217-220 adds white noise
+to the STFT coefficients).  The kernels are maavss_rir_synth and maavss_reverb (include/maavss.h, csrc/reverb.hip);
+tests/reverb_twin.py restates both definitions in float64.
+
+    h[0] = 1, h[k] = 0 for 1 <= k < predelay, h[k] = s g[k] exp(-ln(1000) k / (rt60 sr)) behind it, g standard normal,
+    s such that 10 log10(1 / sum_{k >= predelay} h[k]^2) = drr_db                               (wet = dry + tail)
+    wet[b, n] = sum_k h[rir_index[b], k] audio[b, n - k]      in f64, one order of additions, rounded once to f32
+
+The samples in front of a clip are read where they lie: `lead` samples in front of every row of a tensor, or, for the clips of a
+ClipBank, the clip's recording back to its first sample (never a neighbouring recording).  A clip convolved from a zero state would
+be mostly build-up: a room of rt60 = 0.5 s remembers more than a 0.53 s clip holds.
+"""
+import math
+
+import torch
+
+from . import _lib
+from ._lib import call, ptr, stream_ptr
+
+TARGETS = ("wet", "dry")
+
+
+def _range(name, v, positive=False):
+    lo, hi = (float(x) for x in v)
+    if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi or (positive and lo <= 0.0):
+        raise ValueError(f"{name} must be a finite {'positive ' if positive else ''}range (lo, hi) with lo <= hi, got {v!r}")
+    return lo, hi
+
+
+def _positive_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    return v
+
+
+def bank_floor(bank, indices):
+    """The first sample of the recording each clip belongs to, CPU int64 [B] in bank coordinates, from the tables
+    bank.check_indices(indices) has built (call that first: it validates the indices)."""
+    ends, _, _, sample0, _ = bank._tables
+    idx = indices.to(torch.int64) if isinstance(indices, torch.Tensor) else torch.tensor(list(indices), dtype=torch.int64)
+    return sample0[torch.bucketize(idx, ends, right=True)]
+
+
+class Reverb:
+    """`reverb = Reverb(rir_len, sr=16000, rt60=(lo, hi), drr_db=(lo, hi), predelay_ms=(lo, hi))`; `reverb.make_rirs(64, seed=e)` once
+    per epoch; `wet = reverb(audio, seed=s)` or `wet = reverb.bank_clips(bank, indices, seed=s)` per batch.
+
+    rir_len K: taps per response, 1 <= K <= 32768 (a response is cut there: choose K >= rt60 * sr to keep 60 dB of it).  The ranges
+    are what sample() draws from; make_rirs also takes explicit per-room values."""
+
+    def __init__(self, rir_len, sr=16000, rt60=(0.2, 0.8), drr_db=(0.0, 12.0), predelay_ms=(1.0, 5.0), device="cuda"):
+        k = _positive_int("rir_len", rir_len)
+        if k > 32768:
+            raise ValueError(f"rir_len must be at most 32768 taps, got {k}")
+        if isinstance(sr, bool) or not isinstance(sr, (int, float)) or not (math.isfinite(sr) and sr > 0):
+            raise ValueError(f"sr must be a positive number, got {sr!r}")
+        self.rir_len, self.sr = k, sr
+        self.rt60 = _range("rt60", rt60, positive=True)
+        self.drr_db = _range("drr_db", drr_db)
+        self.predelay_ms = _range("predelay_ms", predelay_ms)
+        if self.predelay_ms[0] < 0.0:
+            raise ValueError(f"predelay_ms must not be negative, got {predelay_ms!r}")
+        self.device = torch.device(device)
+        self.rirs = None                      # the current table [n, K] on the device, what make_rirs made last
+
+    # ---- host logic: draws and refusals, no device work ---------------------------------------------------
+    def sample(self, n, generator):
+        """-> (rt60 [n] f64 seconds, drr_db [n] f64, predelay [n] int32 samples), CPU tensors drawn from `generator` (a CPU
+        torch.Generator).  Draw order: ONE torch.rand(3, n, float64); row 0 gives rt60 = lo + (hi - lo) u, row 1 drr_db likewise,
+        row 2 predelay = max(1, round((lo + (hi - lo) u) * sr / 1000)) samples (the direct path keeps lag 0 to itself)."""
+        _positive_int("n", n)
+        u = torch.rand(3, n, generator=generator, dtype=torch.float64)
+        (r0, r1), (d0, d1), (p0, p1) = self.rt60, self.drr_db, self.predelay_ms
+        pre = ((p0 + (p1 - p0) * u[2]) * (self.sr / 1000.0)).round().clamp(min=1.0).to(torch.int32)
+        return r0 + (r1 - r0) * u[0], d0 + (d1 - d0) * u[1], pre
+
+    def check_params(self, n, rt60, drr_db, predelay):
+        """Every refusal of make_rirs' per-room values -> params f64 [n, 3] = (ln(1000) / (rt60 sr), 10^(drr_db / 10), predelay), the
+        table maavss_rir_synth reads."""
+        rt = torch.as_tensor(rt60, dtype=torch.float64).reshape(-1)
+        dr = torch.as_tensor(drr_db, dtype=torch.float64).reshape(-1)
+        pd = torch.as_tensor(predelay)
+        if pd.dtype.is_floating_point or pd.dtype == torch.bool:
+            raise ValueError(f"predelay must hold integers (samples), got {pd.dtype}")
+        pd = pd.reshape(-1).to(torch.int64)
+        for name, t in (("rt60", rt), ("drr_db", dr), ("predelay", pd)):
+            if t.is_cuda:
+                raise ValueError(f"{name} must be a CPU tensor or a number (its values are checked on the host)")
+            if t.numel() not in (1, n):
+                raise ValueError(f"{name} must be a number or hold {n} values, got {t.numel()}")
+        rt, dr, pd = rt.expand(n), dr.expand(n), pd.expand(n)
+        if not bool((torch.isfinite(rt) & (rt > 0)).all()):
+            raise ValueError("rt60 must be finite and positive")
+        lin = torch.pow(10.0, dr / 10.0)
+        if not bool((torch.isfinite(dr) & torch.isfinite(lin) & (lin > 0)).all()):
+            raise ValueError("drr_db must be finite and 10^(drr_db / 10) a positive float64")
+        if bool((pd < 1).any()):
+            raise ValueError("predelay must be at least 1 sample: lag 0 is the direct path")
+        return torch.stack([math.log(1000.0) / (rt * self.sr), lin, pd.to(torch.float64)], dim=1).contiguous()
+
+    def sample_index(self, batch, generator):
+        """-> CPU int32 [batch]: one room of the current table per clip, uniformly, one torch.randint(0, n, (batch,))."""
+        _positive_int("batch", batch)
+        if self.rirs is None:
+            raise ValueError("no room responses yet: call make_rirs first")
+        return torch.randint(0, self.rirs.shape[0], (batch,), generator=generator, dtype=torch.int32)
+
+    def check_index(self, batch, rir_index, seed):
+        """rir_index as given, or drawn from `seed` -> CPU int32 [batch], every entry inside the current table."""
+        if self.rirs is None:
+            raise ValueError("no room responses yet: call make_rirs first")
+        if rir_index is None:
+            return self.sample_index(batch, torch.Generator().manual_seed(seed))
+        if not isinstance(rir_index, torch.Tensor) or rir_index.dtype != torch.int32 or tuple(rir_index.shape) != (batch,):
+            raise ValueError(f"rir_index must be an int32 [{batch}] tensor, got {getattr(rir_index, 'dtype', type(rir_index))} "
+                             f"{tuple(getattr(rir_index, 'shape', ()))}")
+        if rir_index.is_cuda:
+            raise ValueError("rir_index must be a CPU tensor (its values are checked on the host, like crop boxes)")
+        n = self.rirs.shape[0]
+        if bool(((rir_index < 0) | (rir_index >= n)).any()):
+            raise ValueError(f"rir_index entries must be in [0, {n}), got [{int(rir_index.min())}, {int(rir_index.max())}]")
+        return rir_index.contiguous()
+
+    def check(self, audio, rir_index=None, seed=0, lead=0):
+        """Every refusal of __call__, from shapes, dtypes and values alone (no device work) -> rir_index (CPU int32 [B]).  `audio` is
+        the [B, L] tensor or, when it does not exist yet, the pair (B, L)."""
+        if isinstance(lead, bool) or not isinstance(lead, int) or lead < 0:
+            raise ValueError(f"lead must be a non-negative integer, got {lead!r}")
+        if isinstance(audio, torch.Tensor):
+            if audio.dim() != 2 or audio.dtype != torch.float32 or (audio.shape[1] > 1 and audio.stride(1) != 1) or audio.stride(0) < 0:
+                raise ValueError(f"audio must be float32 [B, L] with unit last stride, got {audio.dtype} {tuple(audio.shape)} strides {audio.stride()}")
+            b, length = audio.shape
+            if lead > audio.storage_offset():
+                raise ValueError(f"lead={lead}: only {audio.storage_offset()} samples of the tensor's storage lie in front of its first row")
+        else:
+            b, length = audio
+            if lead:
+                raise ValueError("lead needs the tensor whose storage holds the history")
+        if b < 1 or length < 1:
+            raise ValueError(f"audio needs at least one clip and one sample, got [B, L] = {(b, length)}")
+        return self.check_index(b, rir_index, seed)
+
+    # ---- device work ----------------------------------------------------------------------------------------
+    def make_rirs(self, n, seed=0, rt60=None, drr_db=None, predelay=None, noise=None):
+        """A table of n room responses [n, K] on the device, kept as `reverb.rirs` and returned.  rt60 (s), drr_db, predelay (samples,
+        >= 1): numbers or n values on the CPU; those not given are self.sample(n, torch.Generator().manual_seed(seed))'s.  noise [n, K]
+        f32 on the device: the normals g; by default the kernel draws them from `seed` (row r the same whatever n is).  The
+        parameters reach the device in one non-blocking copy from pinned memory; one launch on the current stream."""
+        _positive_int("n", n)
+        if n > 1 << 19:
+            raise ValueError(f"a table holds at most {1 << 19} responses, got {n}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        if rt60 is None or drr_db is None or predelay is None:
+            drawn = self.sample(n, torch.Generator().manual_seed(seed))
+            rt60 = drawn[0] if rt60 is None else rt60
+            drr_db = drawn[1] if drr_db is None else drr_db
+            predelay = drawn[2] if predelay is None else predelay
+        params = self.check_params(n, rt60, drr_db, predelay)
+        k = self.rir_len
+        if noise is not None and (not isinstance(noise, torch.Tensor) or noise.dtype != torch.float32 or tuple(noise.shape) != (n, k)
+                                  or (k > 1 and noise.stride(1) != 1) or noise.stride(0) < (k if n > 1 else 0)):
+            raise ValueError(f"noise must be a float32 [{n}, {k}] tensor with unit last stride and rows that do not overlap, got "
+                             f"{getattr(noise, 'dtype', type(noise))} {tuple(getattr(noise, 'shape', ()))}")
+        rirs = torch.empty(n, k, device=self.device, dtype=torch.float32)
+        _lib.require_cuda(rirs, noise)
+        staged = torch.empty(n, 3, device=self.device, dtype=torch.float64)
+        staged.copy_(params.pin_memory(), non_blocking=True)
+        call("maavss_rir_synth", ptr(staged), ptr(noise), (noise.stride(0) if n > 1 else k) if noise is not None else 0, seed, 0, n, k,
+             ptr(rirs), k, stream_ptr())
+        self.rirs = rirs
+        return rirs
+
+    def _convolve(self, src_ptr, n_src, start, floor, index, length, out):
+        """The launch behind __call__ and bank_clips: CPU tables start / floor int64 [B] and index int32 [B] in the coordinates of the
+        flat buffer at src_ptr.  The tables go to the device in one copy from pinned memory (the int64 ones first: 8-byte aligned);
+        the entry point checks the pinned copy."""
+        b = start.numel()
+        host = torch.cat([start.contiguous().view(torch.int32), floor.contiguous().view(torch.int32), index]).pin_memory()
+        staged = torch.empty(5 * b, device=self.device, dtype=torch.int32)
+        staged.copy_(host, non_blocking=True)
+        call("maavss_reverb", src_ptr, n_src, ptr(staged), ptr(staged[2 * b:]), ptr(host), ptr(host[2 * b:]), b, length, ptr(self.rirs),
+             self.rirs.shape[0], self.rirs.stride(0), self.rir_len, ptr(staged[4 * b:]), ptr(host[4 * b:]), ptr(out),
+             out.stride(0) if b > 1 else length, stream_ptr())
+        return out
+
+    def __call__(self, audio, rir_index=None, *, seed=0, lead=0):
+        """audio [B, L] f32 on the device (rows may be strided and may overlap) -> wet [B, L]: row b convolved with room rir_index[b]
+        (CPU int32 [B]; by default self.sample_index(B, torch.Generator().manual_seed(seed))).  lead=P: the P samples in front of
+        every row (in the tensor's storage, e.g. the row's past in a longer recording) are its history; by default a row starts from
+        zero state.  Everything is checked before any device work; no synchronisation; all work goes to the current stream."""
+        index = self.check(audio, rir_index, seed, lead)
+        _lib.require_cuda(audio, self.rirs)
+        b, length = audio.shape
+        stride = audio.stride(0) if b > 1 else 0
+        floor = torch.arange(b, dtype=torch.int64) * stride
+        out = torch.empty(b, length, device=audio.device, dtype=torch.float32)
+        return self._convolve(audio.data_ptr() - 4 * lead, lead + (b - 1) * stride + length, floor + lead, floor, index, length, out)
+
+    def check_bank(self, bank, n, rir_index, seed, out=None):
+        """bank_clips' refusals behind bank.check_indices -> rir_index (CPU int32 [n])."""
+        index = self.check_index(n, rir_index, seed)
+        a, b = bank.device, self.device                     # "cuda" names the current device: it goes with any index
+        if a.type != b.type or (a.index is not None and b.index is not None and a.index != b.index):
+            raise ValueError(f"the bank is on {bank.device}, the room responses on {self.device}")
+        length = bank.clip_samples
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, length) or out.dtype != torch.float32
+                                or (length > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < length)):
+            raise ValueError(f"out must be a float32 {[n, length]} tensor with unit last stride and rows that do not overlap, got "
+                             f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+        return index
+
+    def bank_clips(self, bank, indices, rir_index=None, *, seed=0, out=None):
+        """The clips `indices` of a ClipBank (as bank.batch takes them), wet: convolved from bank.audio where it lies, each clip hearing
+        its own recording's past back to the recording's first sample and never a neighbouring recording -> [B, clip_samples] f32
+        (`out`, when given).  With a one-tap table [[1]] these are bank.batch's audio clips bit for bit."""
+        _, start = bank.check_indices(indices)
+        index = self.check_bank(bank, start.numel(), rir_index, seed, out)
+        return self.cut(bank, start, bank_floor(bank, indices), index, out=out)
+
+    def cut(self, bank, start, floor, index, *, out=None):
+        """bank_clips behind its checks: CPU tables in bank coordinates."""
+        _lib.require_cuda(bank.audio, self.rirs, out)
+        if out is None:
+            out = torch.empty(start.numel(), bank.clip_samples, device=self.device, dtype=torch.float32)
+        return self._convolve(bank.audio.data_ptr(), bank.n_samples, start, floor, index, bank.clip_samples, out)
