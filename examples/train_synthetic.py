@@ -13,6 +13,8 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --reverb 16 [--reverb_target dry]      # every clip in one of 16 synthetic rooms, new rooms every epoch
                                                                               # (maavss_amd.Reverb; with --bank a clip hears its recording's
                                                                               # past); dry: the target stays the dry clip (dereverberation)
+    python examples/train_synthetic.py --reverb 16 --rooms image --mix 1      # 16 shoebox rooms (image-source model) of 2 sources: a clip and
+                                                                              # its partner are heard in the same room
     python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
     python examples/train_synthetic.py --val 2                                # every 2 steps: held-out loss and LSD, a checkpoint on improvement
     python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
@@ -65,6 +67,11 @@ def main():
     ap.add_argument("--mix_snr", type=float, nargs=2, default=(0.0, 10.0), metavar=("LO", "HI"), help="with --mix: signal-to-interferer range in dB")
     ap.add_argument("--reverb", type=int, default=0, metavar="N",
                     help="convolve every clip with one of N synthetic room responses of 0.5 s (maavss_amd.Reverb), N new rooms every epoch")
+    ap.add_argument("--rooms", choices=("noise", "image"), default="noise",
+                    help="with --reverb: decaying-noise responses (Reverb.make_rirs), or N shoebox rooms by the image-source model "
+                         "(Reverb.sample_rooms + make_room_rirs); with --mix K every clip and its K partners are sources of one room")
+    ap.add_argument("--room_sources", type=int, default=None, metavar="S",
+                    help="with --rooms image: source positions per room (default: K + 1 with --mix K, else 1)")
     ap.add_argument("--reverb_target", choices=("wet", "dry"), default="wet",
                     help="with --reverb: the target is the reverberant clip (wet) or the dry one (dry: not together with --mix)")
     ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM",
@@ -106,6 +113,12 @@ def main():
         ap.error("--bank holds transformed frames' maps and 16 kHz audio: it does not go with --raw_video, --raw_audio or --overfit")
     if a.reverb and a.reverb_target == "dry" and a.mix:
         ap.error("--reverb_target dry does not go with --mix: the target of a reverberant mixture is not built")
+    if a.rooms == "image" and not a.reverb:
+        ap.error("--rooms image chooses how --reverb N fills its table: it goes with --reverb")
+    room_sources = a.room_sources if a.room_sources is not None else a.mix + 1
+    if a.rooms == "image" and a.mix and (room_sources < a.mix + 1 or a.batch % (a.mix + 1)):
+        ap.error(f"--rooms image with --mix {a.mix}: groups of {a.mix + 1} clips share a room, so --room_sources must be at least {a.mix + 1} "
+                 f"and --batch a multiple of it")
     dev = torch.device("cuda:0")
     b, nf, ns, w, hpf = a.batch, a.num_frames, a.num_seq, a.framesize, a.hops_per_frame
     t_total = nf + ns - 1                                      # frames per clip so that num_seq windows fit (av_dataset.py:251-278)
@@ -135,8 +148,26 @@ def main():
         raw_length = audio_transform.input_length(length, raw_sr)      # the fewest 44.1 kHz samples that give `length` at 16 kHz
     mixer = maavss_amd.Mixer(stft, a.mix, tuple(a.mix_snr)) if a.mix else None
     reverb = maavss_amd.Reverb(8000, rt60=(0.2, 0.5), device=dev) if a.reverb else None
+
+    def make_rooms(seed):
+        """The epoch's table: N decaying-noise responses, or N image-source rooms of room_sources sources each."""
+        if a.rooms == "image":
+            dims, mic, sources, rt60 = reverb.sample_rooms(a.reverb, torch.Generator().manual_seed(seed), sources=room_sources)
+            reverb.make_room_rirs(dims, mic, sources, rt60=rt60)
+        else:
+            reverb.make_rirs(a.reverb, seed=seed)
+
+    def room_kw(seed):
+        """--rooms image with --mix K: consecutive groups of K + 1 clips are the sources of one room and each other's partners."""
+        if a.rooms != "image" or not a.mix:
+            return {}
+        group = a.mix + 1
+        member = torch.arange(b, dtype=torch.int32).view(-1, group)
+        partners = torch.stack([torch.cat([member[:, :j], member[:, j + 1:]], dim=1) for j in range(group)], dim=1).reshape(b, a.mix)
+        return dict(partners=partners.contiguous(), rir_index=reverb.sample_room_index(b, torch.Generator().manual_seed(seed), group))
+
     if reverb is not None:
-        reverb.make_rirs(a.reverb, seed=0)                       # epoch 0's rooms; submit() below makes the later ones
+        make_rooms(0)                                            # epoch 0's rooms; submit() below makes the later ones
     if not a.bank:
         pipe = maavss_amd.ClipPipeline(extractor, stft, clip_frames=t_total, transform=transform, audio_transform=audio_transform,
                                        audio_length=length if a.raw_audio else None, mixer=mixer, reverb=reverb, reverb_target=a.reverb_target)
@@ -171,7 +202,7 @@ def main():
 
     if not a.bank:
         def submit(seed):
-            pipe.submit(*(fixed or batch()), seed=seed, **sr_arg)
+            pipe.submit(*(fixed or batch()), seed=seed, **sr_arg, **room_kw(seed))
     else:
         # the reference's cached attention frames and audio memmap (train_avse_frames.py:50, av_dataset.py:136-147), on the device: every
         # recording goes through the ViT once, here; clip k of a recording starts frame_hop frames after clip k - 1
@@ -210,12 +241,12 @@ def main():
             epochs = batches()
 
             def submit(seed):
-                pipe.submit_clips(next(epochs), seed=seed)
+                pipe.submit_clips(next(epochs), seed=seed, **room_kw(seed))
         else:
             def submit(seed):
                 while len(order) < b:                                    # the next epoch's permutation of the training clips
                     order.extend(torch.randperm(n_train, generator=g_order).tolist())
-                pipe.submit_clips([order.pop(0) for _ in range(b)], seed=seed)
+                pipe.submit_clips([order.pop(0) for _ in range(b)], seed=seed, **room_kw(seed))
 
     if reverb is not None:
         # an epoch: the sampler's, or one pass over the bank's training clips, or (clips drawn on the fly) 8 steps
@@ -227,7 +258,7 @@ def main():
                 # the side stream may still read the old table: keep its memory until that work is done.  The new one is written on
                 # this stream in front of the submit, which the side stream waits for
                 reverb.rirs.record_stream(pipe.side)
-                reverb.make_rirs(a.reverb, seed=seed // epoch_steps)
+                make_rooms(seed // epoch_steps)
             submit_clips(seed)
 
     held_out = validator = val_dir = None
@@ -236,13 +267,13 @@ def main():
         if a.select:
             held = maavss_amd.ClipSampler(bank, b, recordings=range(a.bank, n_rec), shuffle=False, **limits)      # the split by file
             print(f"select: {held.accepted.numel()} of {held.n_considered} held-out clips accepted", flush=True)
-            pipe.submit_clips(next(held.epoch(0)), seed=12345)
+            pipe.submit_clips(next(held.epoch(0)), seed=12345, **room_kw(12345))
         elif a.bank:
-            pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345)
+            pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345, **room_kw(12345))
         else:
             g_train, g = g, torch.Generator().manual_seed(12345)
             frames_v, audio_v = batch()
-            pipe.submit(frames_v, audio_v, seed=12345, **sr_arg)
+            pipe.submit(frames_v, audio_v, seed=12345, **sr_arg, **room_kw(12345))
             g = g_train
             if mixer is not None and not a.raw_audio:
                 # what kind of error the held-out mixtures hold before any separation (BSS-eval, maavss_amd.bss_eval_metrics): the same

@@ -867,6 +867,39 @@ int maavss_reverb(const float* src, int64_t n_src, const int64_t* start, const i
                   const int64_t* host_floor, int64_t B, int64_t L, const float* rirs, int64_t n_rirs, int64_t ld_rir, int K,
                   const int32_t* rir_index, const int32_t* host_rir_index, float* out, int64_t ld_out, void* stream);
 
+/* ---- EXTENSION: image-source room responses (maavss_amd.Reverb.make_room_rirs) ----------------------------------------------------
+ * A second way to fill the table maavss_reverb convolves with: the image-source model of a shoebox room (Allen & Berkley 1979), one
+ * microphone, one source per row; rows that share dimensions, microphone and walls are sources of one room.  tests/room_twin.py
+ * restates the definition in float64 and the kernel gives its bytes.  Additive symbol (nothing existing changed meaning).
+ *
+ * Row r of geom f64 [n_rows][15] = (L[3], m[3], s[3], beta[6]): room dimensions in metres, microphone, source (both strictly inside
+ * the room and not on each other), pressure reflection coefficients of the walls x0 x1 y0 y1 z0 z1 in [0, 1].  Row r of bounds int32
+ * [n_rows][3] = (Nx, Ny, Nz).  Per axis a, lattice index n in [-N_a, N_a] and parity p in {0, 1}:
+ *   u_a = ((2 n) L_a + (1 - 2 p) s_a) - m_a,  reflected |n - p| times off wall a0 and |n| times off wall a1;
+ *   d = sqrt((ux ux + uy uy) + uz uz);  d0 the same for n = 0, p = 0 on all axes (the direct path);
+ *   A = (((((x0^e1 * x1^e2) * y0^e3) * y1^e4) * z0^e5) * z1^e6) * d0) / d,  integer powers by
+ *       r = 1; while (e) { if (e & 1) r = r * b; b = b * b; e >>= 1; }   (0^0 = 1: a wall of beta = 0 is anechoic, the direct path stays);
+ *   tau = (d - d0) * (sr / c),  k0 = floor(tau),  f = tau - k0:  a response is normalised to its own direct path and starts at it,
+ *       so the direct path adds exactly 1 to h[0] (wet = dry + reflections, aligned with the dry signal as maavss_rir_synth's is);
+ *   for m = -H + 1 .. H, tap k = k0 + m with 0 <= k < K (others are dropped, not folded) receives A * w,
+ *       pos = ((m - f) + H) * R,  i = min(floor(pos), 2 H R - 1),  t = pos - i,  w = T[i] + t * (T[i + 1] - T[i]);
+ *   T = table, f64 [2 H R + 1], the caller's: a windowed sinc sampled at x = i / R - H with exact zeros at the integers and an exact 1
+ *       at x = 0 keeps an image that falls on a sample a clean impulse (T[2 H R] = 0 makes w = 0 exactly at pos = 2 H R).  No device
+ *       sin or cos enters.
+ *   Fixed point: q = llrint((A * w) * 2^40) (ties to even) as int64; a tap is the integer sum of its q; h[k] = f32((double)sum * 2^-40).
+ * Every f64 operation is rounded on its own in the order written (the file is compiled without contraction; sqrt and / are the
+ * correctly rounded ones).  Integer addition is associative: the order of the images, the tiling and the launch cannot change a bit, no
+ * float atomic is involved, and a row in a table has the bytes of a table of its own.  |A w| <= 1 and a row has at most 2^31 images
+ * (8 (2 Nx + 1)(2 Ny + 1)(2 Nz + 1), refused above that), so the sum stays below 2^62.
+ * Which images are evaluated: those of the lattice box.  With 2 N_a L_a >= d0 + (K + H) c / sr on every axis no image outside the box
+ * reaches a tap below K, and any larger box gives the same bytes; a smaller one truncates the response.
+ * geom, bounds, table: device memory (8-, 4-, 8-byte aligned); host_geom, host_bounds: the same tables in host memory, checked row by
+ * row before the launch (a NaN fails every check).  1 <= K <= 32768, 1 <= H <= 32, 1 <= R <= 256, n_rows <= 2^19, ld_rir >= K; the
+ * padding of rirs is not written.  No allocation, no synchronisation, no workspace.  One launch: a workgroup per (row, 1024 taps)
+ * accumulates its taps as int64 in LDS from the shell of images that can reach them and writes them once. */
+int maavss_room_rir(const double* geom, const int32_t* bounds, const double* host_geom, const int32_t* host_bounds, int64_t n_rows,
+                    const double* table, int H, int R, double sr, double c, int K, float* rirs, int64_t ld_rir, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,10 @@ tests/reverb_twin.py restates both definitions in float64.
 The samples in front of a clip are read where they lie: `lead` samples in front of every row of a tensor, or, for the clips of a
 ClipBank, the clip's recording back to its first sample (never a neighbouring recording).  A clip convolved from a zero state would
 be mostly build-up: a room of rt60 = 0.5 s remembers more than a 0.53 s clip holds.
+
+make_room_rirs fills the same table from geometry instead: the image-source model of a shoebox room with one microphone and S sources
+(maavss_room_rir, csrc/room_rir.hip; tests/room_twin.py restates the definition in float64 and the kernel gives its bytes).  Row
+room * S + j is source j of a room, so clips that are given rows of one room (sample_room_index) are sources heard in the same walls.
 """
 import math
 
@@ -31,6 +35,12 @@ def _range(name, v, positive=False):
 def _positive_int(name, v):
     if isinstance(v, bool) or not isinstance(v, int) or v < 1:
         raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    return v
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
     return v
 
 
@@ -62,7 +72,8 @@ class Reverb:
         if self.predelay_ms[0] < 0.0:
             raise ValueError(f"predelay_ms must not be negative, got {predelay_ms!r}")
         self.device = torch.device(device)
-        self.rirs = None                      # the current table [n, K] on the device, what make_rirs made last
+        self.rirs = None                      # the current table [n, K] on the device, what make_rirs / make_room_rirs made last
+        self.sources_per_room = None          # S when make_room_rirs made the table (row room * S + j), None for make_rirs' rooms
 
     # ---- host logic: draws and refusals, no device work ---------------------------------------------------
     def sample(self, n, generator):
@@ -98,6 +109,149 @@ class Reverb:
         if bool((pd < 1).any()):
             raise ValueError("predelay must be at least 1 sample: lag 0 is the direct path")
         return torch.stack([math.log(1000.0) / (rt * self.sr), lin, pd.to(torch.float64)], dim=1).contiguous()
+
+    # ---- image-source rooms: host logic --------------------------------------------------------------------
+    @staticmethod
+    def kernel_table(half_width=8, resolution=32):
+        """The fractional-delay kernel maavss_room_rir interpolates in: T f64 [2 H R + 1], g(x) = sinc(x) (1 + cos(pi x / H)) / 2 at
+        x = i / R - H, with the entries at integer x set to exactly 0 and the one at x = 0 to exactly 1 (an image that falls on a
+        sample stays a clean impulse)."""
+        h, r = _int_in("half_width", half_width, 1, 32), _int_in("resolution", resolution, 1, 256)
+        x = torch.arange(2 * h * r + 1, dtype=torch.float64) / r - h
+        t = torch.sinc(x) * (0.5 * (1.0 + torch.cos(math.pi * x / h)))
+        t[::r] = 0.0
+        t[h * r] = 1.0
+        return t
+
+    @staticmethod
+    def eyring_beta(dims, rt60):
+        """dims [n, 3] metres, rt60 [n] seconds (CPU, f64) -> beta f64 [n, 6] = exp(-0.0805 V / (A_surf rt60)), the same on all six
+        walls, clamped into [0, 1]: Eyring's formula (rt60 = 0.161 V / (-A_surf ln(1 - alpha)), beta^2 = 1 - alpha) solved for beta.
+        This is a NOMINAL figure.  An image-source shoebox with uniform walls decays more slowly than Eyring predicts, because the
+        axial paths graze fewer walls than a diffuse field does: a CPU prototype of the definition measured T20 of 0.46, 0.85 and
+        0.37 s for nominal 0.30, 0.50 and 0.25 s in three rooms (profiles/room_rir_decay.json holds the float64 twin's ratios)."""
+        d = torch.as_tensor(dims, dtype=torch.float64).reshape(-1, 3)
+        rt = torch.as_tensor(rt60, dtype=torch.float64).reshape(-1)
+        if rt.numel() not in (1, d.shape[0]):
+            raise ValueError(f"rt60 must be a number or hold {d.shape[0]} values, got {rt.numel()}")
+        if not bool((torch.isfinite(d) & (d > 0)).all()) or not bool((torch.isfinite(rt) & (rt > 0)).all()):
+            raise ValueError("dims and rt60 must be finite and positive")
+        volume = d[:, 0] * d[:, 1] * d[:, 2]
+        surface = 2.0 * (d[:, 0] * d[:, 1] + d[:, 1] * d[:, 2] + d[:, 0] * d[:, 2])
+        beta = torch.exp(-0.0805 * volume / (surface * rt)).clamp(0.0, 1.0)
+        return beta[:, None].expand(-1, 6).contiguous()
+
+    def sample_rooms(self, n, generator, sources=1, dims=((3.0, 8.0), (3.0, 8.0), (2.4, 3.5)), rt60=None, wall_margin=0.3, min_distance=0.5):
+        """-> (dims [n, 3], mic [n, 3], sources [n, S, 3], rt60 [n]), CPU f64 tensors drawn from `generator` (a CPU torch.Generator).
+        Draw order: ONE torch.rand(n, 7 + 3 S, float64) u; columns 0-2 give the dimensions lo + (hi - lo) u from the three `dims`
+        ranges, column 3 rt60 likewise (from `rt60`, by default the instance's range), columns 4-6 the microphone
+        wall_margin + (L - 2 wall_margin) u per axis, columns 7 + 3 j .. 9 + 3 j source j the same way.  Then, while any source lies
+        closer than min_distance to its microphone: ONE torch.rand(bad, 3, float64) redraws those sources, in (room, source) order, by
+        the same rule; after 64 rounds that still leave one too close the arguments are refused."""
+        _positive_int("n", n)
+        s = _positive_int("sources", sources)
+        ranges = [_range(f"dims[{a}]", dims[a], positive=True) for a in range(3)] if len(dims) == 3 else None
+        if ranges is None:
+            raise ValueError(f"dims must be three (lo, hi) ranges, got {dims!r}")
+        r0, r1 = self.rt60 if rt60 is None else _range("rt60", rt60, positive=True)
+        margin, dist = float(wall_margin), float(min_distance)
+        if not (math.isfinite(margin) and margin > 0.0 and math.isfinite(dist) and dist >= 0.0):
+            raise ValueError(f"wall_margin must be positive and min_distance non-negative, got {wall_margin!r}, {min_distance!r}")
+        if min(lo for lo, _ in ranges) <= 2.0 * margin:
+            raise ValueError(f"the smallest room of {dims!r} leaves no space inside wall_margin = {margin}")
+        u = torch.rand(n, 7 + 3 * s, generator=generator, dtype=torch.float64)
+        lo = torch.tensor([v[0] for v in ranges], dtype=torch.float64)
+        hi = torch.tensor([v[1] for v in ranges], dtype=torch.float64)
+        size = lo + (hi - lo) * u[:, 0:3]
+        span = size - 2.0 * margin
+        mic = margin + span * u[:, 4:7]
+        src = margin + span[:, None, :] * u[:, 7:].reshape(n, s, 3)
+        for _ in range(64):
+            bad = ((src - mic[:, None, :]) ** 2).sum(dim=2).sqrt() < dist
+            if not bool(bad.any()):
+                return size, mic, src, r0 + (r1 - r0) * u[:, 3]
+            room = bad.nonzero()[:, 0]
+            src[bad] = margin + span[room] * torch.rand(int(bad.sum()), 3, generator=generator, dtype=torch.float64)
+        raise ValueError(f"min_distance = {dist} leaves sources too close to the microphone after 64 redraws: the rooms are too small for it")
+
+    def check_rooms(self, dims, mic, sources, beta=None, rt60=None, c=343.0, half_width=8, resolution=32):
+        """Every refusal of make_room_rirs, from values alone (no device work) -> (geom f64 [n S, 15] = (L, m, s, beta) per row,
+        bounds int32 [n S, 3], table f64 [2 H R + 1], S).  The lattice bounds: N_a = floor(Rmax / (2 L_a)) + 1 with
+        Rmax = d0 + (K + H) c / sr, beyond which no image reaches a tap below K."""
+        table = self.kernel_table(half_width, resolution)
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not (math.isfinite(c) and c > 0):
+            raise ValueError(f"c must be a positive number (m/s), got {c!r}")
+        if (beta is None) == (rt60 is None):
+            raise ValueError("exactly one of beta [n, 6] and rt60 [n] must be given")
+        tensors = {}
+        for name, v in (("dims", dims), ("mic", mic), ("sources", sources), ("beta", beta), ("rt60", rt60)):
+            if v is None:
+                continue
+            if isinstance(v, torch.Tensor) and v.is_cuda:
+                raise ValueError(f"{name} must be a CPU tensor or nested lists (its values are checked on the host)")
+            tensors[name] = torch.as_tensor(v, dtype=torch.float64)
+        d, m, src = tensors["dims"], tensors["mic"], tensors["sources"]
+        if d.dim() != 2 or d.shape[1] != 3 or d.shape[0] < 1:
+            raise ValueError(f"dims must be [n, 3], got {tuple(d.shape)}")
+        n = d.shape[0]
+        if tuple(m.shape) != (n, 3):
+            raise ValueError(f"mic must be [{n}, 3], got {tuple(m.shape)}")
+        if src.dim() != 3 or src.shape[0] != n or src.shape[1] < 1 or src.shape[2] != 3:
+            raise ValueError(f"sources must be [{n}, S, 3] with S >= 1, got {tuple(src.shape)}")
+        s = src.shape[1]
+        if n * s > 1 << 19:
+            raise ValueError(f"a table holds at most {1 << 19} responses, got {n} rooms x {s} sources")
+        if not bool((torch.isfinite(d) & (d > 0)).all()):
+            raise ValueError("dims must be finite and positive")
+        if not bool(((m > 0) & (m < d)).all()):
+            raise ValueError("every microphone must lie strictly inside its room (not on a wall)")
+        if not bool(((src > 0) & (src < d[:, None, :])).all()):
+            raise ValueError("every source must lie strictly inside its room (not on a wall)")
+        if rt60 is not None:
+            rt = tensors["rt60"].reshape(-1)
+            if rt.numel() not in (1, n):
+                raise ValueError(f"rt60 must be a number or hold {n} values, got {rt.numel()}")
+            b = self.eyring_beta(d, rt)
+        else:
+            b = tensors["beta"]
+            if tuple(b.shape) != (n, 6):
+                raise ValueError(f"beta must be [{n}, 6] (walls x0 x1 y0 y1 z0 z1), got {tuple(b.shape)}")
+            if not bool(((b >= 0) & (b <= 1)).all()):
+                raise ValueError("beta must lie in [0, 1]")
+        diff = src - m[:, None, :]
+        d0 = ((diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]).sqrt()         # [n, S]
+        if not bool((d0 > 0).all()):
+            raise ValueError("a source lies on its microphone")
+        rmax = d0 + (self.rir_len + half_width) * float(c) / float(self.sr)
+        bounds = torch.floor(rmax[..., None] / (2.0 * d[:, None, :])) + 1.0                                            # [n, S, 3]
+        images = 8.0 * (2.0 * bounds + 1.0).prod(dim=2)
+        if not bool((images <= float(1 << 31)).all()):
+            r = int((images > float(1 << 31)).nonzero()[0, 0])
+            raise ValueError(f"room {r} ({d[r].tolist()} m) needs a lattice box of {images[r].max().item():.3g} images for {self.rir_len} taps, "
+                             f"above the cap of 2^31")
+        geom = torch.cat([d[:, None, :].expand(n, s, 3), m[:, None, :].expand(n, s, 3), src, b[:, None, :].expand(n, s, 6)], dim=2)
+        return geom.reshape(n * s, 15).contiguous(), bounds.to(torch.int32).reshape(n * s, 3).contiguous(), table, s
+
+    def sample_room_index(self, batch, generator, group):
+        """-> CPU int32 [batch]: consecutive groups of `group` clips share one room of the current make_room_rirs table, drawn
+        uniformly, and get distinct sources of it.  Draw order: ONE torch.randint(0, rooms, (batch / group,)), then ONE
+        torch.rand(batch / group, S, float64) whose rows' argsort gives each group's sources in clip order (its first `group`
+        entries).  With a Mixer whose partners stay inside the group, a target and its interferers are heard in one room."""
+        _positive_int("batch", batch)
+        _positive_int("group", group)
+        if self.rirs is None:
+            raise ValueError("no room responses yet: call make_room_rirs first")
+        if self.sources_per_room is None:
+            raise ValueError("the current table is make_rirs': its rows are unrelated rooms (make_room_rirs makes rooms with several sources)")
+        s = self.sources_per_room
+        if group > s:
+            raise ValueError(f"group = {group} clips need as many distinct sources, the rooms have {s}")
+        if batch % group:
+            raise ValueError(f"batch = {batch} is no multiple of group = {group}")
+        groups = batch // group
+        room = torch.randint(0, self.rirs.shape[0] // s, (groups,), generator=generator)
+        src = torch.rand(groups, s, generator=generator, dtype=torch.float64).argsort(dim=1)[:, :group]
+        return (room[:, None] * s + src).reshape(batch).to(torch.int32)
 
     def sample_index(self, batch, generator):
         """-> CPU int32 [batch]: one room of the current table per clip, uniformly, one torch.randint(0, n, (batch,))."""
@@ -169,8 +323,36 @@ class Reverb:
         staged.copy_(params.pin_memory(), non_blocking=True)
         call("maavss_rir_synth", ptr(staged), ptr(noise), (noise.stride(0) if n > 1 else k) if noise is not None else 0, seed, 0, n, k,
              ptr(rirs), k, stream_ptr())
-        self.rirs = rirs
+        self.rirs, self.sources_per_room = rirs, None
         return rirs
+
+    def make_room_rirs(self, dims, mic, sources, *, beta=None, rt60=None, c=343.0, half_width=8, resolution=32):
+        """A table of image-source responses [n S, K] on the device, kept as `reverb.rirs` and returned; row room * S + j is source j
+        of a room and `reverb.sources_per_room` = S.  dims [n, 3], mic [n, 3], sources [n, S, 3]: CPU tensors or nested lists, metres,
+        positions strictly inside the room.  Exactly one of beta [n, 6] (pressure reflection coefficients of the walls x0 x1 y0 y1 z0
+        z1, in [0, 1]) and rt60 [n] (seconds: eyring_beta's nominal figure on all six walls).  c: speed of sound; half_width H and
+        resolution R: the fractional-delay kernel (kernel_table).  Every response is normalised to its direct path, which sits at
+        lag 0.  Everything is checked before any device work; kernel table, geometry and lattice bounds reach the device in one
+        non-blocking copy from pinned memory; one launch on the current stream, no synchronisation."""
+        geom, bounds, table, s = self.check_rooms(dims, mic, sources, beta, rt60, c, half_width, resolution)
+        rirs = torch.empty(geom.shape[0], self.rir_len, device=self.device, dtype=torch.float32)
+        self._fill_rooms(geom, bounds, table, half_width, resolution, c, rirs)
+        self.rirs, self.sources_per_room = rirs, s
+        return rirs
+
+    def _fill_rooms(self, geom, bounds, table, half_width, resolution, c, rirs):
+        """The launch behind make_room_rirs: check_rooms' CPU tables into rirs [rows, K] (unit last stride).  Table, geometry and
+        bounds travel as one f64 block (the int32 bounds last, two to a slot); the entry point checks the pinned copy."""
+        _lib.require_cuda(rirs)
+        rows, n_tab = geom.shape[0], table.numel()
+        packed = torch.zeros((3 * rows + 1) // 2 * 2, dtype=torch.int32)
+        packed[:3 * rows] = bounds.reshape(-1)
+        host = torch.cat([table, geom.reshape(-1), packed.view(torch.float64)]).pin_memory()
+        staged = torch.empty(host.numel(), device=self.device, dtype=torch.float64)
+        staged.copy_(host, non_blocking=True)
+        call("maavss_room_rir", ptr(staged[n_tab:]), ptr(staged[n_tab + 15 * rows:]), ptr(host[n_tab:]), ptr(host[n_tab + 15 * rows:]), rows,
+             ptr(staged), half_width, resolution, float(self.sr), float(c), self.rir_len, ptr(rirs), rirs.stride(0) if rows > 1 else self.rir_len,
+             stream_ptr())
 
     def _convolve(self, src_ptr, n_src, start, floor, index, length, out):
         """The launch behind __call__ and bank_clips: CPU tables start / floor int64 [B] and index int32 [B] in the coordinates of the
