@@ -35,8 +35,10 @@ extern "C" {
  *        the affine part; epilogue 4 of maavss_vit_ws_gemm (GELU in packed half); the in-kernel noise of maavss_stft_fwd draws the bin n_fft / 2
  *        from its own per-frame-pair Philox block (same seed, different noise in that bin); maavss_bn_pool_act_fwd and
  *        maavss_conv3d_c1_bn_pool_act take an out_bf16 pointer behind out16, maavss_conv3d_wgrad's dy16 became the mask in16; see INTEGRATION.md
- *   401  maavss_convt2d_{out_size,fwd,dgrad,wgrad_nchunk,wgrad} removed: the STFT decoder runs through maavss_conv2d_gen_* (<= 30 taps) */
-#define MAAVSS_ABI_VERSION 401
+ *   401  maavss_convt2d_{out_size,fwd,dgrad,wgrad_nchunk,wgrad} removed: the STFT decoder runs through maavss_conv2d_gen_* (<= 30 taps)
+ *   402  maavss_conv2d_{fwd,dgrad,wgrad_nchunk,wgrad} removed: the STFT encoder runs through maavss_conv2d_gen_*, which launch its (3,9)
+ *        kernels when the call is such a layer; the size of maavss_conv2d_gen_wgrad's ws comes from maavss_conv2d_gen_wgrad_ws_bytes */
+#define MAAVSS_ABI_VERSION 402
 const char* maavss_last_error(void);
 int maavss_version(void);
 const char* maavss_arch(void);
@@ -225,25 +227,20 @@ int maavss_bn_pool_act_bwd_finish(const float* dout, const float* out, const voi
                                   float* coef, int B, int T, int H, int W, int C, int pool, int act, int64_t os_b,
                                   int64_t os_t, int64_t os_p, int64_t os_c, int dy_bf16, void* stream);
 
-/* ---- K10 Conv2d(k=(3,9), stride (sh,sw), pad (1,pw), bias=False) -- avse_model_final.py:98-102 ----
- * in_layout 0: x NCHW [B][Ci][H][W] (network input), 1: NHWC; y/dy NHWC [B][Ho][Wo][Co]; w [Co][Ci][3][9].
- * wgrad ws: maavss_conv2d_wgrad_nchunk(B,Ho,Wo,Ci,Co) * Co*Ci*27 floats. */
-int maavss_conv2d_fwd(const float* x, const float* w, float* y, int B, int Ci, int H, int W, int Co, int sh, int sw,
-                      int pw, int in_layout, void* stream);
-int maavss_conv2d_dgrad(const float* dy, const float* w, float* dx, int B, int Ci, int H, int W, int Co, int sh,
-                        int sw, int pw, void* stream);
-int maavss_conv2d_wgrad_nchunk(int B, int Ho, int Wo, int Ci, int Co);
-int maavss_conv2d_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int Ci, int H, int W, int Co,
-                        int sh, int sw, int pw, int in_layout, int beta, void* stream);
-
-/* ---- K19 generic Conv2d / ConvTranspose2d (bias nullable) of the phasegram variant avse_model.AV_Fusion_Model
- * (avse_model.py:433,452,494,591): kernels (1,9) and (5,5), any stride / padding, <= 30 taps, also the
- * STFT decoder (avse_model_final.py:155-193: ConvTranspose2d (3,9) / (3,10), padding (1,4), bias=False; formerly K11).
+/* ---- K19 Conv2d / ConvTranspose2d (bias nullable): the phasegram variant avse_model.AV_Fusion_Model
+ * (avse_model.py:433,452,494,591): kernels (1,9) and (5,5), any stride / padding, <= 30 taps, the
+ * STFT decoder (avse_model_final.py:155-193: ConvTranspose2d (3,9) / (3,10), padding (1,4), bias=False; formerly K11) and the
+ * STFT encoder (K10; avse_model_final.py:98-102: Conv2d (3,9), stride in {1,2}^2, padding (1,pw), bias=False).
  * A small map S [B][Hs][Ws][Cs] and a big map G [B][Hb][Wb][Cb] with by = sy*sh - ph + kh, bx = sx*sw - pw + kw and a
  * weight w[cs][cb][kh][kw] (= Conv2d's [Co][Ci] and ConvTranspose2d's [Ci][Co]):
  *   gen_small: S = bias + G (*) w   -- Conv2d forward, ConvTranspose2d input gradient (bias NULL)
  *   gen_big:   G = bias + S (*)^T w -- ConvTranspose2d forward, Conv2d input gradient (bias NULL)
- *   gen_wgrad: dw = S (x) G         -- both; ws: maavss_conv2d_gen_wgrad_nchunk(B,Hs,Ws) * Cs*Cb*kh*kw floats
+ *   gen_wgrad: dw = S (x) G         -- both; ws: maavss_conv2d_gen_wgrad_ws_bytes(the same geometry) bytes
+ * A call without bias that is an encoder layer -- kernel (3,9), ph = 1, pw <= 8, strides in {1,2}^2, S dense NHWC of the size the
+ * convolution arithmetic gives, G dense NHWC (gen_small, gen_wgrad: or dense NCHW), Cs in {4,8,16} with Cb <= 16 (gen_small), Cs in
+ * {4,8,12,16} with Cb in {2,4,8,16} (gen_big), Cs in {4,8,16} (gen_wgrad) -- launches one-thread-per-position kernels and a weight
+ * gradient of one partial per >= 1024 positions; every other call one-thread-per-element kernels and one partial per
+ * maavss_conv2d_gen_wgrad_nchunk(B,Hs,Ws) = 4096 positions.  Which of the two runs is part of the result's last bits.
  * small_strides / big_strides: HOST arrays of 4 element strides {batch, y, x, channel} (NCHW and channels-last, also
  * channel-padded, without copies).  channel_sum: out[c] (+)= sum_rows x[row*row_stride + c*chan_stride] (bias gradients). */
 int maavss_conv2d_gen_small(const float* big, const float* w, const float* bias, float* small, int B, int Cs, int Hs, int Ws,
@@ -253,6 +250,8 @@ int maavss_conv2d_gen_big(const float* small, const float* w, const float* bias,
                           int Cb, int Hb, int Wb, int kh, int kw, int sh, int sw, int ph, int pw,
                           const int64_t* small_strides, const int64_t* big_strides, void* stream);
 int maavss_conv2d_gen_wgrad_nchunk(int B, int Hs, int Ws);
+int64_t maavss_conv2d_gen_wgrad_ws_bytes(int B, int Cs, int Hs, int Ws, int Cb, int Hb, int Wb, int kh, int kw, int sh, int sw, int ph,
+                                         int pw, const int64_t* small_strides, const int64_t* big_strides);
 int maavss_conv2d_gen_wgrad(const float* small, const float* big, float* dw, float* ws, int B, int Cs, int Hs, int Ws, int Cb,
                             int Hb, int Wb, int kh, int kw, int sh, int sw, int ph, int pw, const int64_t* small_strides,
                             const int64_t* big_strides, int beta, void* stream);

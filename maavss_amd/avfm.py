@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._engine import (bilstm_dseq, bilstm_fwd, bilstm_wgrad_operands, bn_eval_reduce, bn_stats_padded, cpad, mark_touched,
-                      pad_c)
+from ._engine import (bilstm_dseq, bilstm_fwd, bilstm_wgrad_operands, bn_eval_reduce, mark_touched, stack_backward, stack_forward,
+                      stack_layers)
 
 FUSED_DIM, LSTM_HIDDEN, SLOPE = 512, 256, 0.3
 
@@ -92,11 +92,8 @@ class _Fn(torch.autograd.Function):
         model = ctx.model
         names = model._names[ctx.mode]
         need = {n: ctx.needs_input_grad[2 + ctx.n_in + i] for i, n in enumerate(names)}
-        model._bn_eval = not ctx.was_training       # eval-mode forward: BatchNorm backward without the batch-mean terms
-        try:
-            grads = model._run_backward(ctx.mode, ctx.saved, d_outs, need)
-        finally:
-            model._bn_eval = False
+        # eval-mode forward: BatchNorm backward without the batch-mean terms
+        grads = model._run_backward(ctx.mode, ctx.saved, d_outs, need, bn_eval_reduce if not ctx.was_training else None)
         ctx.saved = None
         mark_touched(model, grads)
         return (None, None) + (None,) * ctx.n_in + tuple(grads.get(n) for n in names)
@@ -178,20 +175,12 @@ class AV_Fusion_Model(nn.Module):
         self.a_fc1 = nn.Sequential(nn.Linear(FUSED_DIM, 2 * self.t_a * self.n_bins), nn.LeakyReLU(negative_slope=SLOPE))
         self.v_fc1 = nn.Sequential(nn.Linear(FUSED_DIM, self.h * self.w_full), nn.LeakyReLU(negative_slope=SLOPE))
 
-        # engine descriptors: (prefix, index of the conv module in its Sequential, kind, stride, pad, has_bn)
-        def stack(prefix, mods, kind, strides, pads, bns):
-            out, idx = [], 0
-            for st, pd_, bn in zip(strides, pads, bns):
-                out.append(dict(prefix=prefix, idx=idx, kind=kind, stride=st, pad=pd_, bn=bn))
-                idx += 3 if bn else 1
-            assert idx == len(mods)
-            return out
-
+        # engine descriptors (_engine.stack_layers)
         self._stacks = {
-            "pgram_enc": stack("phasegram_encoder", self.phasegram_encoder, "conv", [(1, 2)] * len(pe), [(0, 4)] * len(pe), [True] * len(pe)),
-            "pgram_dec": stack("phasegram_decoder", self.phasegram_decoder, "convT", [(1, 2)] * len(pd), [(0, 4)] * len(pd), [p[2] for p in pd]),
-            "stft_enc": stack("stft_encoder", self.stft_encoder, "conv", [p[2] for p in se], [(2, 2)] * len(se), [True] * len(se)),
-            "stft_dec": stack("stft_decoder", self.stft_decoder, "convT", [p[2] for p in sd], [(2, 2)] * len(sd), [p[4] for p in sd]),
+            "pgram_enc": stack_layers(self.phasegram_encoder, "phasegram_encoder", "conv", [(1, 2)] * len(pe), [(0, 4)] * len(pe), [True] * len(pe)),
+            "pgram_dec": stack_layers(self.phasegram_decoder, "phasegram_decoder", "convT", [(1, 2)] * len(pd), [(0, 4)] * len(pd), [p[2] for p in pd]),
+            "stft_enc": stack_layers(self.stft_encoder, "stft_encoder", "conv", [p[2] for p in se], [(2, 2)] * len(se), [True] * len(se)),
+            "stft_dec": stack_layers(self.stft_decoder, "stft_decoder", "convT", [p[2] for p in sd], [(2, 2)] * len(sd), [p[4] for p in sd]),
         }
         all_names = [n for n, _ in self.named_parameters()]      # shared modules are listed once, under their first name
         self._names = {
@@ -248,127 +237,20 @@ class AV_Fusion_Model(nn.Module):
         pd = dict(self.named_parameters())
         return _FusionFn.apply(self, x_a, x_v, *[pd[n] for n in _FUSION_PARAMS])
 
-    # ---- engine: convolution stacks ---------------------------------------------------------------------------
-    def _mods(self, layer):
-        seq = getattr(self, layer["prefix"])
-        conv = seq[layer["idx"]]
-        return conv, (seq[layer["idx"] + 1] if layer["bn"] else None)
-
-    def _stack_forward(self, name, x_map, train, final_nchw=False, seq_out=None):
-        """x_map: ops.Map of the input.  Runs conv(+bias) -> BN -> tanh per layer.  `seq_out` = (buffer, element offset,
-        strides) makes the last layer's BN+tanh write straight into the LSTM sequence buffer.  Returns (output, saved)."""
-        saved, cur = [], x_map
-        layers = self._stacks[name]
-        b = x_map.b
-        for li, layer in enumerate(layers):
-            conv, bn = self._mods(layer)
-            w, bias = conv.weight.detach(), conv.bias.detach()
-            st, pd_ = layer["stride"], layer["pad"]
-            kh, kw = w.shape[2], w.shape[3]
-            last = li == len(layers) - 1
-            if layer["kind"] == "conv":
-                co = w.shape[0]
-                ho, wo = (cur.h + 2 * pd_[0] - kh) // st[0] + 1, (cur.w + 2 * pd_[1] - kw) // st[1] + 1
-            else:
-                co = w.shape[1]
-                op = conv.output_padding
-                ho, wo = (cur.h - 1) * st[0] - 2 * pd_[0] + kh + op[0], (cur.w - 1) * st[1] - 2 * pd_[1] + kw + op[1]
-            if bn is None and final_nchw:
-                y = torch.empty(b, co, ho, wo, device=cur.t.device, dtype=torch.float32)
-                ymap = ops.Map(y, nchw=True)
-            else:
-                cp = cpad(co) if bn is not None else co
-                y = torch.zeros(b, ho, wo, cp, device=cur.t.device, dtype=torch.float32) if cp != co else \
-                    torch.empty(b, ho, wo, cp, device=cur.t.device, dtype=torch.float32)
-                ymap = ops.Map(y, c=co)
-            if layer["kind"] == "conv":
-                ops.conv_gen_small(cur, w, bias, ymap, st, pd_)
-            else:
-                ops.conv_gen_big(cur, w, bias, ymap, st, pd_)
-            rec = dict(x=cur, y=ymap)
-            if bn is not None:
-                cp = y.shape[-1]
-                mean, invstd = bn_stats_padded(y, bn, co, b * ho * wo, train)
-                gamma, beta = pad_c(bn.weight.detach(), cp), pad_c(bn.bias.detach(), cp)
-                y5 = y.view(b, ho, 1, wo, cp)                   # "T" = rows, one spatial row each: strides per row / column
-                if last and seq_out is not None:
-                    buf, off, strides = seq_out
-                    assert cp == co
-                    out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, gamma, beta, 1, ops.BN_TANH, out=buf.view(-1)[off:], strides=strides)
-                    rec.update(y5=y5, mean=mean, invstd=invstd, gamma=gamma, out=out, strides=strides)
-                    cur = None
-                else:
-                    out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, gamma, beta, 1, ops.BN_TANH)
-                    rec.update(y5=y5, mean=mean, invstd=invstd, gamma=gamma, out=out, strides=None)
-                    cur = ops.Map(out.view(b, ho, wo, cp), c=co)
-            else:
-                cur = ymap
-            saved.append(rec)
-        return cur, saved
-
-    def _stack_backward(self, name, saved, dcur, need, grads, want_dx=False, dcur_strided=None):
-        """dcur: gradient w.r.t. the stack output -- a tensor shaped like the last layer's output (NHWC padded / NCHW), or
-        `dcur_strided` = (flat buffer view, out view) for an output that lives in the LSTM sequence buffer."""
-        layers = self._stacks[name]
-        dx = None
-        for li in reversed(range(len(layers))):
-            layer, s = layers[li], saved[li]
-            conv, bn = self._mods(layer)
-            prefix, idx = layer["prefix"], layer["idx"]
-            w = conv.weight.detach()
-            st, pd_ = layer["stride"], layer["pad"]
-            ymap = s["y"]
-            b = ymap.b
-            if bn is not None:
-                cp = s["y5"].shape[-1]
-                gw = torch.empty(cp, device=w.device, dtype=torch.float32)
-                gb = torch.empty(cp, device=w.device, dtype=torch.float32)
-                if s["strides"] is not None:
-                    dout, out = dcur_strided
-                else:
-                    dout, out = dcur.view(s["y5"].shape), s["out"]
-                dy = ops.bn_pool_act_bwd(dout, out, None, s["y5"], s["mean"], s["invstd"], s["gamma"], 1, ops.BN_TANH,
-                                         strides=s["strides"], dgamma=gw, dbeta=gb,
-                                         reduce_fn=bn_eval_reduce if getattr(self, "_bn_eval", False) else None)
-                if need.get(f"{prefix}.{idx + 1}.weight", False):
-                    grads[f"{prefix}.{idx + 1}.weight"] = gw[:ymap.c].clone()
-                if need.get(f"{prefix}.{idx + 1}.bias", False):
-                    grads[f"{prefix}.{idx + 1}.bias"] = gb[:ymap.c].clone()
-                dymap = ops.Map(dy.view(b, ymap.h, ymap.w, cp), c=ymap.c)
-            else:
-                dymap = ops.Map(dcur, nchw=ymap.nchw, c=ymap.c)
-            if need.get(f"{prefix}.{idx}.bias", False):
-                grads[f"{prefix}.{idx}.bias"] = ops.channel_sum(dymap)
-            if need.get(f"{prefix}.{idx}.weight", False):
-                if layer["kind"] == "conv":
-                    grads[f"{prefix}.{idx}.weight"] = ops.conv_gen_wgrad(dymap, s["x"], w.shape, st, pd_)
-                else:
-                    grads[f"{prefix}.{idx}.weight"] = ops.conv_gen_wgrad(s["x"], dymap, w.shape, st, pd_)
-            if li > 0 or want_dx:
-                xm = s["x"]
-                dxt = torch.zeros_like(xm.t) if xm.c != xm.c_alloc else torch.empty_like(xm.t)
-                dxm = ops.Map(dxt, nchw=xm.nchw, c=xm.c)
-                if layer["kind"] == "conv":
-                    ops.conv_gen_big(dymap, w, None, dxm, st, pd_)
-                else:
-                    ops.conv_gen_small(dymap, w, None, dxm, st, pd_)
-                dcur, dx = dxt, dxt
-        return dx
-
     # ---- engine: whole network ----------------------------------------------------------------------------------
     def _run_forward(self, mode, inputs):
         train = self.training
         if mode == "visual_ae":
             x_v = inputs[0].contiguous().float()
             assert tuple(x_v.shape[1:]) == (1, self.h, self.w_full)
-            code, s_enc = self._stack_forward("pgram_enc", ops.Map(x_v, nchw=True), train)
-            out, s_dec = self._stack_forward("pgram_dec", code, train, final_nchw=True)
+            code, s_enc = stack_forward(self._stacks["pgram_enc"], ops.Map(x_v, nchw=True), train)
+            out, s_dec = stack_forward(self._stacks["pgram_dec"], code, train, final_nchw=True)
             return out.t, dict(enc=s_enc, dec=s_dec)
         if mode == "audio_ae":
             x_a = inputs[0].contiguous().float()
             assert tuple(x_a.shape[1:]) == (2, self.t_a, self.n_bins)
-            code, s_enc = self._stack_forward("stft_enc", ops.Map(x_a, nchw=True), train)
-            out, s_dec = self._stack_forward("stft_dec", code, train, final_nchw=True)
+            code, s_enc = stack_forward(self._stacks["stft_enc"], ops.Map(x_a, nchw=True), train)
+            out, s_dec = stack_forward(self._stacks["stft_dec"], code, train, final_nchw=True)
             return out.t, dict(enc=s_enc, dec=s_dec)
         x_a, x_v = inputs[0].contiguous().float(), inputs[1].contiguous().float()
         b = x_a.shape[0]
@@ -377,8 +259,8 @@ class AV_Fusion_Model(nn.Module):
         feat = (self.c_v + self.c_a) * w
         seq = torch.empty(b, h, feat, device=dev, dtype=torch.float32)      # cat((x_v, x_a), channel) after permute (0,2,1,3), flattened
         strides = (h * feat, feat, 1, w)                                   # (batch, row, column, channel) of the sequence buffer
-        _, s_v = self._stack_forward("pgram_enc", ops.Map(x_v, nchw=True), train, seq_out=(seq, 0, strides))
-        _, s_a = self._stack_forward("stft_enc", ops.Map(x_a, nchw=True), train, seq_out=(seq, self.c_v * w, strides))
+        _, s_v = stack_forward(self._stacks["pgram_enc"], ops.Map(x_v, nchw=True), train, seq_out=(seq.view(-1), strides))
+        _, s_a = stack_forward(self._stacks["stft_enc"], ops.Map(x_a, nchw=True), train, seq_out=(seq.view(-1)[self.c_v * w:], strides))
         pr = ops.MODE_F32
         saved = dict(s_v=s_v, s_a=s_a, strides=strides)
         fused = self._fusion_fwd(seq, saved)
@@ -423,15 +305,19 @@ class AV_Fusion_Model(nn.Module):
                 grads[nm] = ops.gemm(dz, x, trans_a=True, trans_b=True, precise=pr)
         return dgx
 
-    def _run_backward(self, mode, sv, d_outs, need):
+    def _run_backward(self, mode, sv, d_outs, need, bn_reduce=None):
         grads = {}
+
+        def gbuf(name):      # fresh buffers, nothing to accumulate onto
+            return torch.empty_like(self.get_parameter(name)), 0
+
         if mode in ("visual_ae", "audio_ae"):
             enc, dec = ("pgram_enc", "pgram_dec") if mode == "visual_ae" else ("stft_enc", "stft_dec")
             d = d_outs[0].contiguous().float()
             enc_need = any(need.get(n, False) for n in self._names[mode] if n.startswith(self._stacks[enc][0]["prefix"]))
-            dcode = self._stack_backward(dec, sv["dec"], d, need, grads, want_dx=enc_need)
+            dcode = stack_backward(self._stacks[dec], sv["dec"], d, need, gbuf, grads, bn_reduce=bn_reduce, want_dx=enc_need)
             if enc_need:
-                self._stack_backward(enc, sv["enc"], dcode, need, grads)
+                stack_backward(self._stacks[enc], sv["enc"], dcode, need, gbuf, grads, bn_reduce=bn_reduce)
             return grads
         d_a, d_v, d_fused = d_outs
         pr = ops.MODE_F32
@@ -466,7 +352,7 @@ class AV_Fusion_Model(nn.Module):
             return grads
         dseq = bilstm_dseq(dgx, self.lstm)
         flat_d, flat_o = dseq.view(-1), sv["seq"].view(-1)
-        self._stack_backward("pgram_enc", sv["s_v"], None, need, grads, dcur_strided=(flat_d, flat_o))
+        stack_backward(self._stacks["pgram_enc"], sv["s_v"], flat_d, need, gbuf, grads, out=flat_o, bn_reduce=bn_reduce)
         off = self.c_v * w
-        self._stack_backward("stft_enc", sv["s_a"], None, need, grads, dcur_strided=(flat_d[off:], flat_o[off:]))
+        stack_backward(self._stacks["stft_enc"], sv["s_a"], flat_d[off:], need, gbuf, grads, out=flat_o[off:], bn_reduce=bn_reduce)
         return grads

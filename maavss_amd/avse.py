@@ -24,8 +24,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._engine import (bilstm_dseq, bilstm_fwd, bilstm_wgrad_operands, bn_eval_reduce, bn_stats_padded, cpad, mark_touched,
-                      pad_c)
+from ._engine import (bilstm_dseq, bilstm_fwd, bilstm_wgrad_operands, bn_eval_reduce, bn_grad_bufs, bn_train_stats, mark_touched,
+                      stack_backward, stack_forward, stack_layers)
 
 LSTM_HIDDEN = 256
 FUSED_DIM = 512
@@ -82,24 +82,6 @@ def stft_decoder_plan(t_a, n_bins, t_v, s_v, latent, c_stft):
         kernel = (3, 10) if size[1] == (n_bins - 1) // 2 else (3, 9)
         c_in = c_out
     return plan
-
-
-def _bn_train_stats(part, count, bn, sync):
-    """training-mode (mean, invstd) from the partial sums; `sync` (set_bn_sync) all-reduces them over the data-parallel ranks"""
-    if sync is None:
-        return ops.bn_finalize(part, count, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum)
-    return ops.bn_finalize_synced(part, count, sync, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum)
-
-
-def _bn_grad_bufs(prefix, idx, need, gbuf, out_grads):
-    """(dgamma buffer, dbeta buffer, accumulate) of BatchNorm module `prefix.idx`, entered in out_grads -- or (None, None, False)"""
-    nw, nb = f"{prefix}.{idx}.weight", f"{prefix}.{idx}.bias"
-    if not (need.get(nw, False) or need.get(nb, False)):
-        return None, None, False
-    gw, beta = gbuf(nw)
-    gb, _ = gbuf(nb)
-    out_grads[nw], out_grads[nb] = gw, gb
-    return gw, gb, bool(beta)
 
 
 class _AVSEFunction(torch.autograd.Function):
@@ -252,6 +234,11 @@ class AV_Fusion_Model_Frames(nn.Module):
                     mods += [nn.BatchNorm2d(co), nn.Tanh()]
         self.stft_decoder = nn.Sequential(*mods)
         self.stft_autoencoder = nn.Sequential(*self.stft_encoder, *self.stft_decoder)
+        # engine descriptors (_engine.stack_layers) of the STFT encoder (K10) and decoder
+        self._enc_layers = stack_layers(self.stft_encoder, "stft_encoder", "conv", [p[2] for p in self._enc_plan],
+                                        [(1, p[3]) for p in self._enc_plan], [True] * len(self._enc_plan))
+        self._dec_layers = stack_layers(self.stft_decoder, "stft_decoder", "convT", [p[3] for p in self._dec_plan],
+                                        [ops.CONVT_PAD] * len(self._dec_plan), [p[5] for p in self._dec_plan])
 
         self.a_fc1 = nn.Sequential(nn.Linear(FUSED_DIM, 2 * hops_per_frame * self.n_bins, bias=False))
         self.v_fc1 = nn.Sequential(nn.Linear(FUSED_DIM, self.frame_channels * self.width * self.width, bias=False))
@@ -310,113 +297,24 @@ class AV_Fusion_Model_Frames(nn.Module):
     def _vis(self, i):
         return self.visual_encoder[4 * i], self.visual_encoder[4 * i + 1]
 
-    def _aud(self, i):
-        return self.stft_encoder[3 * i], self.stft_encoder[3 * i + 1]
-
-    # ---- STFT autoencoder engine (K10 + K11) ---------------------------------------------------------------
-    def _dec(self, j):
-        """(ConvTranspose2d, BatchNorm2d or None) of decoder layer j."""
-        idx = 3 * j
-        has_bn = self._dec_plan[j][5]
-        return self.stft_decoder[idx], (self.stft_decoder[idx + 1] if has_bn else None)
-
-    def _stft_encoder_fwd(self, x_a, train, seq_out=None, bn_sync=None):
-        """K10: conv -> BatchNorm -> tanh per layer on x_a [B,2,T_a,F] (NCHW).  `seq_out` = (flat buffer, strides) makes the last
-        layer's BN + tanh write there (the LSTM sequence buffer).  -> (last activation NHWC, or None with seq_out; saved)."""
-        b = x_a.shape[0]
-        saved, cur, nchw = [], x_a, True
-        for i, (ci, co, st, pw) in enumerate(self._enc_plan):
-            conv, bn = self._aud(i)
-            y = ops.conv2d_fwd(cur, conv.weight.detach(), st, pw, nchw)
-            ho, wo = y.shape[1], y.shape[2]
-            if train:
-                mean, invstd = _bn_train_stats(ops.bn_stats(y, co), b * ho * wo, bn, bn_sync)
-            else:
-                mean, invstd = ops.bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
-            y5 = y.view(b, 1, ho, wo, co)
-            buf, strides = seq_out if seq_out is not None and i == len(self._enc_plan) - 1 else (None, None)
-            out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, bn.weight.detach(), bn.bias.detach(), 1, ops.BN_TANH, out=buf, strides=strides)
-            saved.append(dict(x=cur, nchw=nchw, y=y5, mean=mean, invstd=invstd, out=out, strides=strides, hw=(ho, wo)))
-            cur, nchw = out.view(b, ho, wo, co) if strides is None else None, False
-        return cur, saved
-
-    def _stft_encoder_bwd(self, saved, dout, out, strides, bn_reduce, need, gbuf, out_grads):
-        """Backward of _stft_encoder_fwd.  dout / out / strides: gradient and value of the last layer's activation as
-        ops.bn_pool_act_bwd takes them (strided when they live in the LSTM sequence buffer).  `need[name]` says which
-        parameter gradients are wanted, `gbuf(name)` -> (buffer, beta) gives where they go; results are entered in out_grads."""
-        b = saved[0]["x"].shape[0]
-        for i in reversed(range(len(self._enc_plan))):
-            ci, co, st, pw = self._enc_plan[i]
-            conv, bn = self._aud(i)
-            s = saved[i]
-            ho, wo = s["hw"]
-            gw, gb, acc = _bn_grad_bufs("stft_encoder", 3 * i + 1, need, gbuf, out_grads)
-            dy = ops.bn_pool_act_bwd(dout, out, None, s["y"], s["mean"], s["invstd"], bn.weight.detach(), 1, ops.BN_TANH,
-                                     strides=strides, dgamma=gw, dbeta=gb, accumulate=acc, reduce_fn=bn_reduce).view(b, ho, wo, co)
-            wname = f"stft_encoder.{3 * i}.weight"
-            if need.get(wname, False):
-                buf, beta = gbuf(wname)
-                ops.conv2d_wgrad(s["x"], dy, conv.weight.shape, st, pw, s["nchw"], dw=buf, beta=beta)
-                out_grads[wname] = buf
-            if i > 0:
-                below = saved[i - 1]
-                dcur = ops.conv2d_dgrad(dy, conv.weight.detach(), below["hw"], st, pw)
-                dout, out, strides = dcur.view(below["y"].shape), below["out"], None
-
+    # ---- STFT autoencoder engine: both stacks through _engine.stack_forward / stack_backward -----------------------
     def _ae_forward(self, x_a, train=True):
-        b = x_a.shape[0]
         assert tuple(x_a.shape[1:]) == (2, self.t_a, self.n_bins)
-        code, enc = self._stft_encoder_fwd(x_a.contiguous().float(), train)      # per-rank BatchNorm statistics whatever set_bn_sync says
-        sv = {"enc": enc, "dec": []}
-        cur = ops.Map(code)
-        for j, (ci, co, k, st, op, has_bn) in enumerate(self._dec_plan):
-            convt, bn = self._dec(j)
-            ho, wo = ops.convt2d_out(cur.h, cur.w, k[1], st, op)
-            if has_bn:      # channels-last, padded to what the BatchNorm kernels take: the dead channels must be (and stay) exactly zero
-                cp = cpad(co)
-                y = (torch.zeros if cp != co else torch.empty)(b, ho, wo, cp, device=x_a.device, dtype=torch.float32)
-                ymap = ops.Map(y, c=co)
-            else:           # the last layer writes the network's NCHW output
-                ymap = ops.Map(torch.empty(b, co, ho, wo, device=x_a.device, dtype=torch.float32), nchw=True)
-            ops.conv_gen_big(cur, convt.weight.detach(), None, ymap, st, ops.CONVT_PAD)
-            rec = dict(x=cur, y=ymap)
-            if has_bn:
-                mean, invstd = bn_stats_padded(y, bn, co, b * ho * wo, train)
-                gamma = pad_c(bn.weight.detach(), cp)
-                y5 = y.view(b, 1, ho, wo, cp)
-                out, _ = ops.bn_pool_act_fwd(y5, mean, invstd, gamma, pad_c(bn.bias.detach(), cp), 1, ops.BN_TANH)
-                rec.update(y5=y5, mean=mean, invstd=invstd, gamma=gamma, out=out)
-                cur = ops.Map(out.view(b, ho, wo, cp), c=co)
-            else:
-                cur = ymap
-            sv["dec"].append(rec)
-        return cur.t, sv
+        # per-rank BatchNorm statistics whatever set_bn_sync says
+        code, enc = stack_forward(self._enc_layers, ops.Map(x_a.contiguous().float(), nchw=True), train)
+        out, dec = stack_forward(self._dec_layers, code, train, final_nchw=True)
+        return out.t, {"enc": enc, "dec": dec}
 
     def _ae_backward(self, sv, d_out, bn_eval=False):
         grads = {}
         bn_reduce = bn_eval_reduce if bn_eval else None
-        dcur = d_out                                    # NCHW gradient of the last (BN-less) layer's output
-        for j in reversed(range(len(self._dec_plan))):
-            ci, co, k, st, op, has_bn = self._dec_plan[j]
-            s = sv["dec"][j]
-            w = self._dec(j)[0].weight.detach()
-            if has_bn:
-                y5 = s["y5"]
-                gw, gb = torch.empty_like(s["gamma"]), torch.empty_like(s["gamma"])
-                dy = ops.bn_pool_act_bwd(dcur.view(y5.shape), s["out"], None, y5, s["mean"], s["invstd"], s["gamma"], 1,
-                                         ops.BN_TANH, dgamma=gw, dbeta=gb, reduce_fn=bn_reduce)
-                grads[f"stft_decoder.{3 * j + 1}.weight"] = gw[:co].clone()
-                grads[f"stft_decoder.{3 * j + 1}.bias"] = gb[:co].clone()
-                dymap = ops.Map(dy.view(s["y"].t.shape), c=co)
-            else:
-                dymap = ops.Map(dcur, nchw=True)
-            grads[f"stft_decoder.{3 * j}.weight"] = ops.conv_gen_wgrad(s["x"], dymap, w.shape, st, ops.CONVT_PAD)
-            xm = s["x"]
-            dcur = (torch.zeros_like if xm.c != xm.c_alloc else torch.empty_like)(xm.t)
-            ops.conv_gen_small(dymap, w, None, ops.Map(dcur, c=xm.c), st, ops.CONVT_PAD)
-        last = sv["enc"][-1]
-        self._stft_encoder_bwd(sv["enc"], dcur.view(last["y"].shape), last["out"], None, bn_reduce, dict.fromkeys(self._ae_param_names, True),
-                               lambda name: (torch.empty_like(self.get_parameter(name)), 0), grads)      # all needed, fresh buffers
+        need = dict.fromkeys(self._ae_param_names, True)      # all needed, fresh buffers
+
+        def gbuf(name):
+            return torch.empty_like(self.get_parameter(name)), 0
+
+        dcode = stack_backward(self._dec_layers, sv["dec"], d_out, need, gbuf, grads, bn_reduce=bn_reduce, want_dx=True)
+        stack_backward(self._enc_layers, sv["enc"], dcode, need, gbuf, grads, bn_reduce=bn_reduce)
         return grads
 
     def _fusion_fwd(self, seq, sv):
@@ -493,7 +391,7 @@ class AV_Fusion_Model_Frames(nn.Module):
                 y, part = ops.conv3d_igemm(act_in if act_in16 is None else act_in16, wt, co, pad, pr, want_stats=train)
             hh, ww = y.shape[2], y.shape[3]
             if train:
-                mean, invstd = _bn_train_stats(part, b * t * hh * ww, bn, self._bn_sync)
+                mean, invstd = bn_train_stats(part, b * t * hh * ww, bn, self._bn_sync)
             else:
                 mean, invstd = ops.bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
             x_b = act_inb
@@ -519,13 +417,14 @@ class AV_Fusion_Model_Frames(nn.Module):
                                                out=seq, strides=strides)
             sv["vis"].append(dict(x=act_in, x_bf16=x_b, y=y, mean=mean, invstd=invstd, out=out, arg=arg, strides=strides, recompute=recompute))
             act_in = out
-        # --- STFT encoder (K10)
+        # --- STFT encoder (K10): the last layer writes its [B,16,T,S] block of the LSTM sequence like the visual encoder's
         seq_aud = seq.view(-1)[ts:]
-        aud_strides = (self.latent_channels * 2 * ts, 0, 1, 2 * ts)
-        cur, sv["aud"] = self._stft_encoder_fwd(x_a, train, None if self._enc_pool is not None else (seq_aud, aud_strides), self._bn_sync)
+        aud_strides = (self.latent_channels * 2 * ts, self.s_v, 1, 2 * ts)
+        cur, sv["aud"] = stack_forward(self._enc_layers, ops.Map(x_a, nchw=True), train, bn_sync=self._bn_sync,
+                                       seq_out=None if self._enc_pool is not None else (seq_aud, aud_strides))
         if self._enc_pool is not None:
             ho, wo = sv["aud"][-1]["hw"]
-            _lib.call("maavss_adaptive_pool_fwd", cur.data_ptr(), seq_aud.data_ptr(), b, ho, wo, self.latent_channels,
+            _lib.call("maavss_adaptive_pool_fwd", cur.t.data_ptr(), seq_aud.data_ptr(), b, ho, wo, self.latent_channels,
                       self._enc_pool[0], self._enc_pool[1], self.latent_channels * 2 * ts, 1, 2 * ts, _lib.stream_ptr())
         fused = self._fusion_fwd(seq, sv)
         pr = ops.MODE_F32
@@ -599,13 +498,12 @@ class AV_Fusion_Model_Frames(nn.Module):
         # --- STFT encoder backward
         last = sv["aud"][-1]
         if self._enc_pool is not None:
-            dcur = torch.empty(last["y"].shape, device=dseq.device, dtype=torch.float32)
-            _lib.call("maavss_adaptive_pool_bwd", dseq.view(-1)[ts:].data_ptr(), dcur.data_ptr(), b, *last["hw"], l,
+            dout, out = torch.empty_like(last["y"].t), None      # the last layer's own output: its value is last["out"]
+            _lib.call("maavss_adaptive_pool_bwd", dseq.view(-1)[ts:].data_ptr(), dout.data_ptr(), b, *last["hw"], l,
                       self._enc_pool[0], self._enc_pool[1], l * 2 * ts, 1, 2 * ts, _lib.stream_ptr())
-            dout, out = dcur, last["out"]
         else:
             dout, out = dseq.view(-1)[ts:], sv["seq"].view(-1)[ts:]
-        self._stft_encoder_bwd(sv["aud"], dout, out, last["strides"], bn_reduce, need, gbuf, out_grads)
+        stack_backward(self._enc_layers, sv["aud"], dout, need, gbuf, out_grads, out=out, bn_reduce=bn_reduce)
         # --- visual encoder backward
         dcur = None
         for i in reversed(range(5)):
@@ -616,7 +514,7 @@ class AV_Fusion_Model_Frames(nn.Module):
                 dout, out = dseq, sv["seq"]
             else:
                 dout, out = dcur, s["out"]
-            gw, gb, acc = _bn_grad_bufs("visual_encoder", 4 * i + 1, need, gbuf, out_grads)
+            gw, gb, acc = bn_grad_bufs("visual_encoder", 4 * i + 1, need, gbuf, out_grads)
             wname = f"visual_encoder.{4 * i}.weight"
             if i == 0:
                 # first layer: the network input needs no gradient, so dy has one consumer, the weight gradient -- which

@@ -1,73 +1,48 @@
 // K10 (convolution part): the STFT encoder's Conv2d(k=(3,9), stride (sh,sw) in {1,2}^2, pad (1,pw), bias=False)
 // layers (reference avse_model_final.py:98-102), forward / input gradient / weight gradient.
 // 2 -> 4 -> 8 -> 16 (-> 16) channels on at most [128 x 257] maps: a few MFLOP per clip, direct kernels, latency-bound.
-// Round 2: one thread per POSITION with all output (input) channels in registers -- every loaded value feeds C FMAs against
-// wave-uniform weights -- and a weight gradient whose blocks own a (ci, kh) row of 9 taps x all C_out; the first version
-// (one thread per output ELEMENT, one block per (co, ci) pair) re-read each input C times and cost 1.05 ms per step for
-// 0.2 GFLOP.
-// Input layout 0 = NCHW (the network input x_stft [B,2,T_a,F]) or 1 = NHWC; outputs are NHWC.
-// Weights stay in the reference layout [Co][Ci][3][9].
-#include "common.h"
+// One thread per POSITION with all output (input) channels in registers -- every loaded value feeds C FMAs against
+// wave-uniform weights -- and a weight gradient whose blocks own a (ci, kh) row of 9 taps x all C_out; one thread per output
+// ELEMENT, as the generic kernels of conv2d_gen.hip work, re-reads each input C times and cost 1.05 ms per step for 0.2 GFLOP.
+// These are what maavss_conv2d_gen_{small,big,wgrad} launch when the call is such a layer (conv2d_geom.h); every other call
+// runs the generic kernels.  In the terms of CGen the convolution's input x is the big map G (dense NCHW -- the network input
+// x_stft [B,2,T_a,F] -- or dense NHWC), its output y the small map S (dense NHWC); weights stay in the reference layout
+// [Co][Ci][3][9] = [Cs][Cb][3][9].
+#include "conv2d_geom.h"
 
-struct C2Geom {
-  int B, Ci, H, W, Co, Ho, Wo, sh, sw, pw, in_layout;
-};
-
-__device__ __forceinline__ int64_t in_index(const C2Geom& g, int b, int ci, int iy, int ix) {
-  return g.in_layout ? (((int64_t)b * g.H + iy) * g.W + ix) * g.Ci + ci : (((int64_t)b * g.Ci + ci) * g.H + iy) * g.W + ix;
-}
-
-__global__ __launch_bounds__(256) void conv2d_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                         float* __restrict__ y, C2Geom g) {
-  const int64_t total = (int64_t)g.B * g.Ho * g.Wo * g.Co;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int co = (int)(i % g.Co);
-    const int64_t pos = i / g.Co;
-    const int ox = (int)(pos % g.Wo), oy = (int)((pos / g.Wo) % g.Ho), b = (int)(pos / ((int64_t)g.Wo * g.Ho));
-    float acc = 0.f;
-    for (int ci = 0; ci < g.Ci; ++ci)
-      for (int kh = 0; kh < 3; ++kh) {
-        const int iy = oy * g.sh + kh - 1;
-        if (iy < 0 || iy >= g.H) continue;
-        const float* wp = w + (((int64_t)co * g.Ci + ci) * 3 + kh) * 9;
-#pragma unroll
-        for (int kw = 0; kw < 9; ++kw) {
-          const int ix = ox * g.sw + kw - g.pw;
-          if (ix >= 0 && ix < g.W) acc = fmaf(x[in_index(g, b, ci, iy, ix)], wp[kw], acc);
-        }
-      }
-    y[i] = acc;
-  }
+// the big map is dense (the launchers below check it): NHWC when its channel stride is 1, else NCHW
+__device__ __forceinline__ int64_t big_index(const CGen& g, int b, int cb, int by, int bx) {
+  return g.gsc == 1 ? (((int64_t)b * g.Hb + by) * g.Wb + bx) * g.Cb + cb : (((int64_t)b * g.Cb + cb) * g.Hb + by) * g.Wb + bx;
 }
 
 template <int CO>
 __global__ __launch_bounds__(256) void conv2d_fwd_pos_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             float* __restrict__ y, C2Geom g) {
+                                                             float* __restrict__ y, CGen g) {
   // Weights in LDS as [ci][kh][kw][CO]: the CO weights of a tap are CO / 4 broadcast 16-byte reads.  Straight from global memory they were CO
   // scalar loads per tap -- 1.4 scalar-memory instructions per vector instruction, a quarter of the waves' cycles on the scalar unit
   // (profiles/r3_f_scalar_pmc.json).  Same FMA order: results unchanged.
   __shared__ __attribute__((aligned(16))) float wl[16 * 27 * CO];
-  for (int i = threadIdx.x; i < g.Ci * 27 * CO; i += 256) {
+  for (int i = threadIdx.x; i < g.Cb * 27 * CO; i += 256) {
     const int c = i % CO, t = i / CO;                  // t = ci * 27 + kh * 9 + kw
-    wl[i] = w[(int64_t)c * g.Ci * 27 + t];
+    wl[i] = w[(int64_t)c * g.Cb * 27 + t];
   }
   __syncthreads();
-  const int64_t npos = (int64_t)g.B * g.Ho * g.Wo;
+  const int64_t npos = (int64_t)g.B * g.Hs * g.Ws;
   for (int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x; pos < npos; pos += (int64_t)gridDim.x * 256) {
-    const int ox = (int)(pos % g.Wo), oy = (int)((pos / g.Wo) % g.Ho), b = (int)(pos / ((int64_t)g.Wo * g.Ho));
+    const int ox = (int)(pos % g.Ws), oy = (int)((pos / g.Ws) % g.Hs), b = (int)(pos / ((int64_t)g.Ws * g.Hs));
     float acc[CO];
 #pragma unroll
     for (int c = 0; c < CO; ++c) acc[c] = 0.f;
-    for (int ci = 0; ci < g.Ci; ++ci)
+    for (int ci = 0; ci < g.Cb; ++ci)
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh) {
         const int iy = oy * g.sh + kh - 1;
-        const bool oky = iy >= 0 && iy < g.H;
+        const bool oky = iy >= 0 && iy < g.Hb;
 #pragma unroll
         for (int kw = 0; kw < 9; ++kw) {
           const int ix = ox * g.sw + kw - g.pw;
           float v = 0.f;
-          if (oky && ix >= 0 && ix < g.W) v = x[in_index(g, b, ci, iy, ix)];
+          if (oky && ix >= 0 && ix < g.Wb) v = x[big_index(g, b, ci, iy, ix)];
           const float4* wp = reinterpret_cast<const float4*>(wl + ((ci * 3 + kh) * 9 + kw) * CO);
 #pragma unroll
           for (int c = 0; c < CO; c += 4) {
@@ -86,17 +61,17 @@ __global__ __launch_bounds__(256) void conv2d_fwd_pos_kernel(const float* __rest
 // one thread per INPUT position, all CI gradients in registers; dy rows read as float4
 template <int CI>
 __global__ __launch_bounds__(256) void conv2d_dgrad_pos_kernel(const float* __restrict__ dy, const float* __restrict__ w,
-                                                               float* __restrict__ dx, C2Geom g) {
+                                                               float* __restrict__ dx, CGen g) {
   // weights in LDS as [kh][kw][co][CI] (see conv2d_fwd_pos_kernel): the CI weights of (tap, co) are CI / 4 broadcast reads (CI = 2: one 8-byte read)
   __shared__ __attribute__((aligned(16))) float wl[27 * 16 * CI];
-  for (int i = threadIdx.x; i < 27 * g.Co * CI; i += 256) {
-    const int c = i % CI, co = (i / CI) % g.Co, t = i / (CI * g.Co);      // t = kh * 9 + kw
+  for (int i = threadIdx.x; i < 27 * g.Cs * CI; i += 256) {
+    const int c = i % CI, co = (i / CI) % g.Cs, t = i / (CI * g.Cs);      // t = kh * 9 + kw
     wl[i] = w[((int64_t)co * CI + c) * 27 + t];
   }
   __syncthreads();
-  const int64_t npos = (int64_t)g.B * g.H * g.W;
+  const int64_t npos = (int64_t)g.B * g.Hb * g.Wb;
   for (int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x; pos < npos; pos += (int64_t)gridDim.x * 256) {
-    const int ix = (int)(pos % g.W), iy = (int)((pos / g.W) % g.H), b = (int)(pos / ((int64_t)g.W * g.H));
+    const int ix = (int)(pos % g.Wb), iy = (int)((pos / g.Wb) % g.Hb), b = (int)(pos / ((int64_t)g.Wb * g.Hb));
     float acc[CI];
 #pragma unroll
     for (int c = 0; c < CI; ++c) acc[c] = 0.f;
@@ -105,20 +80,20 @@ __global__ __launch_bounds__(256) void conv2d_dgrad_pos_kernel(const float* __re
       const int ty = iy + 1 - kh;
       if (ty < 0 || ty % g.sh != 0) continue;
       const int oy = ty / g.sh;
-      if (oy >= g.Ho) continue;
+      if (oy >= g.Hs) continue;
 #pragma unroll
       for (int kw = 0; kw < 9; ++kw) {
         const int tx = ix + g.pw - kw;
         if (tx < 0 || tx % g.sw != 0) continue;
         const int ox = tx / g.sw;
-        if (ox >= g.Wo) continue;
-        const float4* dp = reinterpret_cast<const float4*>(dy + (((int64_t)b * g.Ho + oy) * g.Wo + ox) * g.Co);
-        for (int c4 = 0; c4 < g.Co / 4; ++c4) {
+        if (ox >= g.Ws) continue;
+        const float4* dp = reinterpret_cast<const float4*>(dy + (((int64_t)b * g.Hs + oy) * g.Ws + ox) * g.Cs);
+        for (int c4 = 0; c4 < g.Cs / 4; ++c4) {
           const float4 d = dp[c4];
           const float dd[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float* wp = wl + ((kh * 9 + kw) * g.Co + c4 * 4 + e) * CI;
+            const float* wp = wl + ((kh * 9 + kw) * g.Cs + c4 * 4 + e) * CI;
             if constexpr (CI % 4 == 0) {
 #pragma unroll
               for (int c = 0; c < CI; c += 4) {
@@ -148,10 +123,10 @@ __global__ __launch_bounds__(256) void conv2d_dgrad_pos_kernel(const float* __re
 // partials[chunk][co][ci][27]; block = ((ci, kh), chunk): 9 taps x all CO accumulators per thread, x row values loaded once
 template <int CO>
 __global__ __launch_bounds__(256) void conv2d_wgrad_row_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                               float* __restrict__ partials, C2Geom g, int64_t pos_per_chunk) {
+                                                               float* __restrict__ partials, CGen g, int64_t pos_per_chunk) {
   __shared__ float red[4][CO * 9];
   const int ci = blockIdx.x / 3, kh = blockIdx.x % 3;
-  const int64_t npos = (int64_t)g.B * g.Ho * g.Wo;
+  const int64_t npos = (int64_t)g.B * g.Hs * g.Ws;
   const int64_t p0 = (int64_t)blockIdx.y * pos_per_chunk, p1 = min(npos, p0 + pos_per_chunk);
   float acc[CO][9];
 #pragma unroll
@@ -159,14 +134,14 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_row_kernel(const float* __re
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[c][k] = 0.f;
   for (int64_t pos = p0 + threadIdx.x; pos < p1; pos += 256) {
-    const int ox = (int)(pos % g.Wo), oy = (int)((pos / g.Wo) % g.Ho), b = (int)(pos / ((int64_t)g.Wo * g.Ho));
+    const int ox = (int)(pos % g.Ws), oy = (int)((pos / g.Ws) % g.Hs), b = (int)(pos / ((int64_t)g.Ws * g.Hs));
     const int iy = oy * g.sh + kh - 1;
-    if (iy < 0 || iy >= g.H) continue;
+    if (iy < 0 || iy >= g.Hb) continue;
     float xv[9];
 #pragma unroll
     for (int kw = 0; kw < 9; ++kw) {
       const int ix = ox * g.sw + kw - g.pw;
-      xv[kw] = (ix >= 0 && ix < g.W) ? x[in_index(g, b, ci, iy, ix)] : 0.f;
+      xv[kw] = (ix >= 0 && ix < g.Wb) ? x[big_index(g, b, ci, iy, ix)] : 0.f;
     }
     const float4* dp = reinterpret_cast<const float4*>(dy + pos * CO);
 #pragma unroll
@@ -190,165 +165,75 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_row_kernel(const float* __re
   __syncthreads();
   for (int i = threadIdx.x; i < CO * 9; i += 256) {
     const int co = i / 9, kw = i % 9;
-    partials[((int64_t)blockIdx.y * CO * g.Ci + (int64_t)co * g.Ci + ci) * 27 + kh * 9 + kw] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    partials[((int64_t)blockIdx.y * CO * g.Cb + (int64_t)co * g.Cb + ci) * 27 + kh * 9 + kw] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
   }
 }
 
-// dx (NHWC) [B][H][W][Ci]
-__global__ __launch_bounds__(256) void conv2d_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
-                                                           float* __restrict__ dx, C2Geom g) {
-  const int64_t total = (int64_t)g.B * g.H * g.W * g.Ci;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int ci = (int)(i % g.Ci);
-    const int64_t pos = i / g.Ci;
-    const int ix = (int)(pos % g.W), iy = (int)((pos / g.W) % g.H), b = (int)(pos / ((int64_t)g.W * g.H));
-    float acc = 0.f;
-    for (int kh = 0; kh < 3; ++kh) {
-      const int ty = iy + 1 - kh;
-      if (ty < 0 || ty % g.sh != 0) continue;
-      const int oy = ty / g.sh;
-      if (oy >= g.Ho) continue;
-#pragma unroll
-      for (int kw = 0; kw < 9; ++kw) {
-        const int tx = ix + g.pw - kw;
-        if (tx < 0 || tx % g.sw != 0) continue;
-        const int ox = tx / g.sw;
-        if (ox >= g.Wo) continue;
-        const float* dp = dy + (((int64_t)b * g.Ho + oy) * g.Wo + ox) * g.Co;
-        for (int co = 0; co < g.Co; ++co) acc = fmaf(dp[co], w[(((int64_t)co * g.Ci + ci) * 3 + kh) * 9 + kw], acc);
-      }
-    }
-    dx[i] = acc;
-  }
-}
-
-// partials[chunk][co][ci][27]; block = (co*Ci+ci, chunk)
-__global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                           float* __restrict__ partials, C2Geom g, int64_t pos_per_chunk) {
-  __shared__ float red[4][27];
-  const int pair = blockIdx.x, co = pair / g.Ci, ci = pair % g.Ci;
-  const int64_t npos = (int64_t)g.B * g.Ho * g.Wo;
-  const int64_t p0 = (int64_t)blockIdx.y * pos_per_chunk, p1 = min(npos, p0 + pos_per_chunk);
-  float acc[27];
-#pragma unroll
-  for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-  for (int64_t pos = p0 + threadIdx.x; pos < p1; pos += 256) {
-    const int ox = (int)(pos % g.Wo), oy = (int)((pos / g.Wo) % g.Ho), b = (int)(pos / ((int64_t)g.Wo * g.Ho));
-    const float d = dy[pos * g.Co + co];
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      const int iy = oy * g.sh + kh - 1;
-      const bool oky = iy >= 0 && iy < g.H;
-#pragma unroll
-      for (int kw = 0; kw < 9; ++kw) {
-        const int ix = ox * g.sw + kw - g.pw;
-        if (oky && ix >= 0 && ix < g.W) acc[kh * 9 + kw] = fmaf(d, x[in_index(g, b, ci, iy, ix)], acc[kh * 9 + kw]);
-      }
-    }
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    const float s = wave_sum(acc[k]);
-    if (lane == 0) red[wv][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 27)
-    partials[((int64_t)blockIdx.y * gridDim.x + pair) * 27 + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// 16 outputs x 16 chunk phases per 256-thread block (one thread per output walking up to 256 chunks serially was a chain of dependent
+// the row kernel's partials through chunk_sum16 (one thread per output walking up to 256 chunks serially was a chain of dependent
 // loads: 60 us for the 216 weights of the first layer); fixed summation order: deterministic
 __global__ __launch_bounds__(256) void conv2d_wgrad_reduce_kernel(const float* __restrict__ partials, float* __restrict__ dw, int n, int nchunk, int beta) {
-  __shared__ float red[16][17];
-  const int o = threadIdx.x & 15, ph = threadIdx.x >> 4, i = blockIdx.x * 16 + o;
-  float s = 0.f;
-  if (i < n)
-    for (int c = ph; c < nchunk; c += 16) s += partials[(int64_t)c * n + i];
-  red[ph][o] = s;
-  __syncthreads();
-  if (ph == 0 && i < n) {
-    float t = 0.f;
-#pragma unroll
-    for (int p = 0; p < 16; ++p) t += red[p][o];
-    dw[i] = beta ? dw[i] + t : t;
-  }
+  bool owner;
+  int i;
+  const float t = chunk_sum16(partials, n, nchunk, blockIdx.x * 16, owner, i);
+  if (owner) dw[i] = beta ? dw[i] + t : t;
 }
 
-static int make_c2geom(const char* who, C2Geom* g, int B, int Ci, int H, int W, int Co, int sh, int sw, int pw, int in_layout) {
-  MAAVSS_CHECK_ARG(B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0, "%s: empty problem", who);
-  MAAVSS_CHECK_ARG((sh == 1 || sh == 2) && (sw == 1 || sw == 2), "%s: stride must be 1 or 2", who);
-  MAAVSS_CHECK_ARG(pw >= 0 && pw <= 8, "%s: bad padding", who);
-  g->B = B; g->Ci = Ci; g->H = H; g->W = W; g->Co = Co; g->sh = sh; g->sw = sw; g->pw = pw; g->in_layout = in_layout;
-  g->Ho = (H + 2 - 3) / sh + 1;
-  g->Wo = (W + 2 * pw - 9) / sw + 1;
-  MAAVSS_CHECK_ARG(g->Ho > 0 && g->Wo > 0, "%s: empty output", who);
-  return MAAVSS_OK;
+// ---- which calls the kernels above were written for.  Strides are compared with ==: a channel-padded map must not reach a
+// kernel that stores float4 rows.
+static bool dense_nhwc(int64_t sb, int64_t sy, int64_t sx, int64_t sc, int C, int H, int W) {
+  return sc == 1 && sx == C && sy == (int64_t)W * C && sb == (int64_t)H * W * C;
 }
+static bool dense_nchw(int64_t sb, int64_t sy, int64_t sx, int64_t sc, int C, int H, int W) {
+  return sx == 1 && sy == W && sc == (int64_t)H * W && sb == (int64_t)C * H * W;
+}
+// kernel (3,9), pad (1, pw <= 8), strides in {1,2}^2, the small map dense NHWC and of the size the convolution arithmetic gives
+static bool k39_layer(const CGen& g) {
+  return g.kh == 3 && g.kw == 9 && g.ph == 1 && g.pw <= 8 && (g.sh == 1 || g.sh == 2) && (g.sw == 1 || g.sw == 2) &&
+         g.Hs == (g.Hb + 2 - 3) / g.sh + 1 && g.Ws == (g.Wb + 2 * g.pw - 9) / g.sw + 1 &&
+         dense_nhwc(g.ssb, g.ssy, g.ssx, g.ssc, g.Cs, g.Hs, g.Ws);
+}
+static bool big_nhwc(const CGen& g) { return dense_nhwc(g.gsb, g.gsy, g.gsx, g.gsc, g.Cb, g.Hb, g.Wb); }
+static bool big_nchw(const CGen& g) { return dense_nchw(g.gsb, g.gsy, g.gsx, g.gsc, g.Cb, g.Hb, g.Wb); }
 
-extern "C" int maavss_conv2d_fwd(const float* x, const float* w, float* y, int B, int Ci, int H, int W, int Co, int sh,
-                                 int sw, int pw, int in_layout, void* stream) {
-  MAAVSS_CHECK_ARG(x && w && y, "conv2d_fwd: null pointer");
-  C2Geom g;
-  if (int rc = make_c2geom("conv2d_fwd", &g, B, Ci, H, W, Co, sh, sw, pw, in_layout)) return rc;
-  const int64_t total = (int64_t)B * g.Ho * g.Wo * Co, npos = (int64_t)B * g.Ho * g.Wo;
+bool conv2d_k39_small(const float* big, const float* w, float* small, const CGen& g, hipStream_t st) {
+  if (!k39_layer(g) || !(big_nhwc(g) || big_nchw(g)) || g.Cb > 16) return false;      // LDS weight image: C_in <= 16
+  const int64_t npos = (int64_t)g.B * g.Hs * g.Ws;
   const dim3 pgrid(min((int64_t)8192, (npos + 255) / 256));
-  hipStream_t st = (hipStream_t)stream;
-  if (Ci > 16) hipLaunchKernelGGL(conv2d_fwd_kernel, dim3(min((int64_t)4096, (total + 255) / 256)), dim3(256), 0, st, x, w, y, g);   // LDS weight image: C_in <= 16
-  else if (Co == 4) hipLaunchKernelGGL(conv2d_fwd_pos_kernel<4>, pgrid, dim3(256), 0, st, x, w, y, g);
-  else if (Co == 8) hipLaunchKernelGGL(conv2d_fwd_pos_kernel<8>, pgrid, dim3(256), 0, st, x, w, y, g);
-  else if (Co == 16) hipLaunchKernelGGL(conv2d_fwd_pos_kernel<16>, pgrid, dim3(256), 0, st, x, w, y, g);
-  else hipLaunchKernelGGL(conv2d_fwd_kernel, dim3(min((int64_t)4096, (total + 255) / 256)), dim3(256), 0, st, x, w, y, g);
-  MAAVSS_LAUNCH_CHECK("conv2d_fwd_kernel");
-  return MAAVSS_OK;
+  if (g.Cs == 4) hipLaunchKernelGGL(conv2d_fwd_pos_kernel<4>, pgrid, dim3(256), 0, st, big, w, small, g);
+  else if (g.Cs == 8) hipLaunchKernelGGL(conv2d_fwd_pos_kernel<8>, pgrid, dim3(256), 0, st, big, w, small, g);
+  else if (g.Cs == 16) hipLaunchKernelGGL(conv2d_fwd_pos_kernel<16>, pgrid, dim3(256), 0, st, big, w, small, g);
+  else return false;
+  return true;
 }
 
-extern "C" int maavss_conv2d_dgrad(const float* dy, const float* w, float* dx, int B, int Ci, int H, int W, int Co, int sh,
-                                   int sw, int pw, void* stream) {
-  MAAVSS_CHECK_ARG(dy && w && dx, "conv2d_dgrad: null pointer");
-  C2Geom g;
-  if (int rc = make_c2geom("conv2d_dgrad", &g, B, Ci, H, W, Co, sh, sw, pw, 1)) return rc;
-  const int64_t total = (int64_t)B * H * W * Ci, npos = (int64_t)B * H * W;
+bool conv2d_k39_big(const float* small, const float* w, float* big, const CGen& g, hipStream_t st) {
+  if (!k39_layer(g) || !big_nhwc(g) || g.Cs > 16 || g.Cs % 4 != 0) return false;      // LDS weight image: C_out <= 16; dy rows as float4
+  const int64_t npos = (int64_t)g.B * g.Hb * g.Wb;
   const dim3 pgrid(min((int64_t)8192, (npos + 255) / 256));
-  hipStream_t st = (hipStream_t)stream;
-  if (Co > 16) hipLaunchKernelGGL(conv2d_dgrad_kernel, dim3(min((int64_t)4096, (total + 255) / 256)), dim3(256), 0, st, dy, w, dx, g);   // LDS weight image: C_out <= 16
-  else if (Co % 4 == 0 && Ci == 2) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<2>, pgrid, dim3(256), 0, st, dy, w, dx, g);
-  else if (Co % 4 == 0 && Ci == 4) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<4>, pgrid, dim3(256), 0, st, dy, w, dx, g);
-  else if (Co % 4 == 0 && Ci == 8) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<8>, pgrid, dim3(256), 0, st, dy, w, dx, g);
-  else if (Co % 4 == 0 && Ci == 16) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<16>, pgrid, dim3(256), 0, st, dy, w, dx, g);
-  else hipLaunchKernelGGL(conv2d_dgrad_kernel, dim3(min((int64_t)4096, (total + 255) / 256)), dim3(256), 0, st, dy, w, dx, g);
-  MAAVSS_LAUNCH_CHECK("conv2d_dgrad_kernel");
-  return MAAVSS_OK;
+  if (g.Cb == 2) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<2>, pgrid, dim3(256), 0, st, small, w, big, g);
+  else if (g.Cb == 4) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<4>, pgrid, dim3(256), 0, st, small, w, big, g);
+  else if (g.Cb == 8) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<8>, pgrid, dim3(256), 0, st, small, w, big, g);
+  else if (g.Cb == 16) hipLaunchKernelGGL(conv2d_dgrad_pos_kernel<16>, pgrid, dim3(256), 0, st, small, w, big, g);
+  else return false;
+  return true;
 }
 
-extern "C" int maavss_conv2d_wgrad_nchunk(int B, int Ho, int Wo, int Ci, int Co) {
-  const int64_t npos = (int64_t)B * Ho * Wo;
-  // blocks = (ci, kh) rows x chunks for the row kernel (C_out in {4, 8, 16}), (co, ci) pairs x chunks otherwise
-  int64_t n = (Co == 4 || Co == 8 || Co == 16) ? 1536 / ((int64_t)Ci * 3) : 1024 / ((int64_t)Ci * Co);
+// blocks = (ci, kh) rows x chunks: as many chunks as fill the device, at least 1024 positions each
+int conv2d_k39_wgrad_nchunk(const CGen& g) {
+  if (!k39_layer(g) || !(big_nhwc(g) || big_nchw(g)) || !(g.Cs == 4 || g.Cs == 8 || g.Cs == 16)) return 0;
+  const int64_t npos = (int64_t)g.B * g.Hs * g.Ws;
+  int64_t n = 1536 / ((int64_t)g.Cb * 3);
   if (n < 1) n = 1;
   if (n > (npos + 1023) / 1024) n = (npos + 1023) / 1024;
-  if (n < 1) n = 1;
   return (int)n;
 }
 
-// ws: nchunk * Co*Ci*27 floats, nchunk = maavss_conv2d_wgrad_nchunk(...)
-extern "C" int maavss_conv2d_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int Ci, int H, int W, int Co,
-                                   int sh, int sw, int pw, int in_layout, int beta, void* stream) {
-  MAAVSS_CHECK_ARG(x && dy && dw && ws, "conv2d_wgrad: null pointer");
-  C2Geom g;
-  if (int rc = make_c2geom("conv2d_wgrad", &g, B, Ci, H, W, Co, sh, sw, pw, in_layout)) return rc;
-  const int nchunk = maavss_conv2d_wgrad_nchunk(B, g.Ho, g.Wo, Ci, Co);
-  const int64_t npos = (int64_t)B * g.Ho * g.Wo;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ppc = (npos + nchunk - 1) / nchunk;
-  if (Co == 4) hipLaunchKernelGGL(conv2d_wgrad_row_kernel<4>, dim3(Ci * 3, nchunk), dim3(256), 0, st, x, dy, ws, g, ppc);
-  else if (Co == 8) hipLaunchKernelGGL(conv2d_wgrad_row_kernel<8>, dim3(Ci * 3, nchunk), dim3(256), 0, st, x, dy, ws, g, ppc);
-  else if (Co == 16) hipLaunchKernelGGL(conv2d_wgrad_row_kernel<16>, dim3(Ci * 3, nchunk), dim3(256), 0, st, x, dy, ws, g, ppc);
-  else hipLaunchKernelGGL(conv2d_wgrad_kernel, dim3(Co * Ci, nchunk), dim3(256), 0, st, x, dy, ws, g, ppc);
-  MAAVSS_LAUNCH_CHECK("conv2d_wgrad_kernel");
-  const int n = Co * Ci * 27;
+void conv2d_k39_wgrad(const float* small, const float* big, float* dw, float* ws, const CGen& g, int nchunk, int beta, hipStream_t st) {
+  const int64_t npos = (int64_t)g.B * g.Hs * g.Ws, ppc = (npos + nchunk - 1) / nchunk;
+  const dim3 grid(g.Cb * 3, nchunk);
+  if (g.Cs == 4) hipLaunchKernelGGL(conv2d_wgrad_row_kernel<4>, grid, dim3(256), 0, st, big, small, ws, g, ppc);
+  else if (g.Cs == 8) hipLaunchKernelGGL(conv2d_wgrad_row_kernel<8>, grid, dim3(256), 0, st, big, small, ws, g, ppc);
+  else hipLaunchKernelGGL(conv2d_wgrad_row_kernel<16>, grid, dim3(256), 0, st, big, small, ws, g, ppc);
+  const int n = g.Cs * g.Cb * 27;
   hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3(cdiv(n, 16)), dim3(256), 0, st, ws, dw, n, nchunk, beta);
-  MAAVSS_LAUNCH_CHECK("conv2d_wgrad_reduce_kernel");
-  return MAAVSS_OK;
 }

@@ -1,10 +1,13 @@
-// K19: every 2-D convolution that is not the STFT encoder's own conv2d.hip.  It serves
+// K19: every 2-D convolution of the library enters here.  It serves
 //   * the biased layers of the phasegram variant avse_model.AV_Fusion_Model (avse_model.py:410-711):
 //     Conv2d / ConvTranspose2d with kernels (1,9) [phasegram encoder / decoder, :433,452] and (5,5) [STFT encoder / decoder,
 //     :494,591], strides in {1,2}^2, bias;
 //   * the bias-free STFT decoder of AV_Fusion_Model_Frames (formerly K11; avse_model_final.py:155-193, audio_ae_forward
 //     :254-256): ConvTranspose2d with kernels (3,9) / (3,10), padding (1,4), strides in {1,2}^2, output_padding = stride - 1
-//     -- (3,10) = 30 taps is what CG_MAX_TAPS is sized for.
+//     -- (3,10) = 30 taps is what CG_MAX_TAPS is sized for;
+//   * the bias-free STFT encoder of AV_Fusion_Model_Frames (K10; avse_model_final.py:98-102): Conv2d (3,9), padding (1,pw).  A call
+//     that is such a layer on dense maps launches the position / row kernels of conv2d.hip (conv2d_geom.h says which calls those
+//     take); that is decided here from the arguments, per call.
 // One formulation serves all of them.  A "small" map S [B][Hs][Ws][Cs] and a "big" map G [B][Hb][Wb][Cb] are
 // tied by  by = sy*sh - ph + kh,  bx = sx*sw - pw + kw  and a weight w[cs][cb][kh][kw]:
 //   gather_small:  S = bias + sum_{cb,kh,kw} G * w      = Conv2d forward (w = [Co][Ci])   = ConvTranspose2d input gradient
@@ -14,13 +17,7 @@
 // Tensors are addressed through explicit element strides (b, y, x, c), so the network's NCHW inputs / outputs and the
 // channels-last activations (optionally channel-padded for the BatchNorm kernels) need no copies.
 // A few MFLOP per clip: direct kernels, one thread per output element; latency / HBM-bound like conv2d.hip.
-#include "common.h"
-
-struct CGen {
-  int B, Cs, Hs, Ws, Cb, Hb, Wb, kh, kw, sh, sw, ph, pw;
-  int64_t ssb, ssy, ssx, ssc;   // strides of the small map
-  int64_t gsb, gsy, gsx, gsc;   // strides of the big map
-};
+#include "conv2d_geom.h"
 
 __global__ __launch_bounds__(256) void cgen_small_kernel(const float* __restrict__ G, const float* __restrict__ w,
                                                          const float* __restrict__ bias, float* __restrict__ S, CGen g) {
@@ -161,8 +158,9 @@ extern "C" int maavss_conv2d_gen_small(const float* big, const float* w, const f
   MAAVSS_CHECK_ARG(big && w && small, "conv2d_gen_small: null pointer");
   CGen g;
   if (int rc = cg_fill(g, B, Cs, Hs, Ws, Cb, Hb, Wb, kh, kw, sh, sw, ph, pw, small_strides, big_strides, "conv2d_gen_small")) return rc;
-  hipLaunchKernelGGL(cgen_small_kernel, dim3(cg_blocks((int64_t)B * Hs * Ws * Cs)), dim3(256), 0, (hipStream_t)stream, big, w, bias, small, g);
-  MAAVSS_LAUNCH_CHECK("cgen_small_kernel");
+  if (bias || !conv2d_k39_small(big, w, small, g, (hipStream_t)stream))
+    hipLaunchKernelGGL(cgen_small_kernel, dim3(cg_blocks((int64_t)B * Hs * Ws * Cs)), dim3(256), 0, (hipStream_t)stream, big, w, bias, small, g);
+  MAAVSS_LAUNCH_CHECK("conv2d_gen_small");
   return MAAVSS_OK;
 }
 
@@ -172,8 +170,9 @@ extern "C" int maavss_conv2d_gen_big(const float* small, const float* w, const f
   MAAVSS_CHECK_ARG(small && w && big, "conv2d_gen_big: null pointer");
   CGen g;
   if (int rc = cg_fill(g, B, Cs, Hs, Ws, Cb, Hb, Wb, kh, kw, sh, sw, ph, pw, small_strides, big_strides, "conv2d_gen_big")) return rc;
-  hipLaunchKernelGGL(cgen_big_kernel, dim3(cg_blocks((int64_t)B * Hb * Wb * Cb)), dim3(256), 0, (hipStream_t)stream, small, w, bias, big, g);
-  MAAVSS_LAUNCH_CHECK("cgen_big_kernel");
+  if (bias || !conv2d_k39_big(small, w, big, g, (hipStream_t)stream))
+    hipLaunchKernelGGL(cgen_big_kernel, dim3(cg_blocks((int64_t)B * Hb * Wb * Cb)), dim3(256), 0, (hipStream_t)stream, small, w, bias, big, g);
+  MAAVSS_LAUNCH_CHECK("conv2d_gen_big");
   return MAAVSS_OK;
 }
 
@@ -182,15 +181,30 @@ extern "C" int maavss_conv2d_gen_wgrad_nchunk(int B, int Hs, int Ws) {
   return (int)(n < 1 ? 1 : (n > 128 ? 128 : n));
 }
 
+// bytes of maavss_conv2d_gen_wgrad's ws for this call: one partial dw per chunk of whichever kernel the call launches (0: a geometry the
+// call itself rejects)
+extern "C" int64_t maavss_conv2d_gen_wgrad_ws_bytes(int B, int Cs, int Hs, int Ws, int Cb, int Hb, int Wb, int kh, int kw, int sh, int sw,
+                                                    int ph, int pw, const int64_t* small_strides, const int64_t* big_strides) {
+  CGen g;
+  if (cg_fill(g, B, Cs, Hs, Ws, Cb, Hb, Wb, kh, kw, sh, sw, ph, pw, small_strides, big_strides, "conv2d_gen_wgrad_ws_bytes")) return 0;
+  const int nrow = conv2d_k39_wgrad_nchunk(g);
+  return (int64_t)(nrow ? nrow : maavss_conv2d_gen_wgrad_nchunk(B, Hs, Ws)) * Cs * Cb * kh * kw * 4;
+}
+
 extern "C" int maavss_conv2d_gen_wgrad(const float* small, const float* big, float* dw, float* ws, int B, int Cs, int Hs, int Ws,
                                        int Cb, int Hb, int Wb, int kh, int kw, int sh, int sw, int ph, int pw,
                                        const int64_t* small_strides, const int64_t* big_strides, int beta, void* stream) {
   MAAVSS_CHECK_ARG(small && big && dw && ws, "conv2d_gen_wgrad: null pointer");
   CGen g;
   if (int rc = cg_fill(g, B, Cs, Hs, Ws, Cb, Hb, Wb, kh, kw, sh, sw, ph, pw, small_strides, big_strides, "conv2d_gen_wgrad")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (const int nrow = conv2d_k39_wgrad_nchunk(g)) {
+    conv2d_k39_wgrad(small, big, dw, ws, g, nrow, beta, st);
+    MAAVSS_LAUNCH_CHECK("conv2d_wgrad_row_kernel");
+    return MAAVSS_OK;
+  }
   const int nchunk = maavss_conv2d_gen_wgrad_nchunk(B, Hs, Ws);
   const int64_t npos = (int64_t)B * Hs * Ws;
-  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(cgen_wgrad_kernel, dim3(Cs * Cb, nchunk), dim3(256), 0, st, small, big, ws, g, (npos + nchunk - 1) / nchunk);
   MAAVSS_LAUNCH_CHECK("cgen_wgrad_kernel");
   const int n = Cs * Cb * kh * kw;

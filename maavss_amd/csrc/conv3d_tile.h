@@ -64,5 +64,5 @@ __device__ __forceinline__ int xcd_chunk(int nchunk) { return (blockIdx.x & 7) *
 // conv3d_wgrad_wide.hip, called by maavss_conv3d_wgrad (conv3d_wgrad.hip)
 int maavss_conv3d_wgrad_wide_try(const float* x, const void* dy, float* ws, int nchunk, int B, int T, int H, int W, int Ho,
                                  int Wo, int c_in, int c_out, int pad, int mode, int dy16, int x16, hipStream_t st);
-// conv3d_wgrad.hip, called by c1_wgrad_launch (conv3d_c1.hip): both reduce kernels sit next to the chunk sum they share (alone in a file the first layer's compiles to another body)
+// conv3d_wgrad.hip, called by c1_wgrad_launch (conv3d_c1.hip): both Conv3d reduce kernels sit in that file, around chunk_sum16 of reduce.h (alone in a file the first layer's compiles to another body)
 void conv3d_c1_wgrad_reduce(const float* ws, float* dw, int nchunk, int beta, hipStream_t st);

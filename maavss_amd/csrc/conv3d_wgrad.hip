@@ -142,25 +142,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(const float* __restri
   }
 }
 
-// Sum of the per-chunk partials: 16 outputs x 16 chunk phases per 256-thread block (one thread per output walking all
-// chunks serially took 70-260 us per layer).
-__device__ __forceinline__ float chunk_sum16(const float* __restrict__ partials, int64_t total, int nchunk, int i0, bool& owner, int& i) {
-  __shared__ float red[16][17];
-  const int o = threadIdx.x & 15, ph = threadIdx.x >> 4;
-  i = i0 + o;
-  float s = 0.f;
-  if (i < total)
-    for (int c = ph; c < nchunk; c += 16) s += partials[(int64_t)c * total + i];
-  red[ph][o] = s;
-  __syncthreads();
-  owner = ph == 0 && i < total;
-  float t = 0.f;
-  if (owner)
-#pragma unroll
-    for (int p = 0; p < 16; ++p) t += red[p][o];
-  return t;
-}
-
 // dW[co][ci][kd][kh][kw] (+)= sum_chunk partials[chunk][kd*5+kh][kw][ci][co]
 __global__ __launch_bounds__(256) void conv3d_wgrad_reduce_kernel(const float* __restrict__ partials, float* __restrict__ dw, int nchunk, int CI,
                                            int CO, int beta) {

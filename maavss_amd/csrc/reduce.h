@@ -8,6 +8,7 @@
 //   WG_SUM                                             the four per-wave results pairwise: (0 + 1) + (2 + 3)
 //   WG_MAX, WG_MIN                                     the NW per-wave results in wave index order: ((0, 1), 2), 3 ...; f32 through
 //                                                      fmaxf / fminf, f64 through the comparison of wave_max_d / wave_min_d
+//   chunk_sum16                                        a weight gradient's per-chunk partials: 16 phases of chunks, then the phases
 // The f32 sums that add their per-wave slots left to right (mse_partial_kernel, vit_cls_attn_kernel, the conv and batch-norm
 // partials) are a third order; they stay written out where they are.
 #pragma once
@@ -129,6 +130,26 @@ __device__ __forceinline__ T wg_reduce(T x, T (&red)[NW][1], int wave, int lane)
   T v[1] = {x};
   wg_reduce<WHO, OP>(v, red, wave, lane);
   return v[0];
+}
+
+// Sum of a weight gradient's per-chunk partials, partials[chunk][total], by a 256-thread block: 16 outputs (i0 ... i0 + 15) x 16 chunk
+// phases (one thread per output walking all chunks serially took 70-260 us per Conv3d layer).  Phase p adds chunks p, p + 16, ...
+// in that order, then the thread of phase 0 (`owner`; it gets the sum of output `i`) adds the 16 phases in index order.
+__device__ __forceinline__ float chunk_sum16(const float* __restrict__ partials, int64_t total, int nchunk, int i0, bool& owner, int& i) {
+  __shared__ float red[16][17];
+  const int o = threadIdx.x & 15, ph = threadIdx.x >> 4;
+  i = i0 + o;
+  float s = 0.f;
+  if (i < total)
+    for (int c = ph; c < nchunk; c += 16) s += partials[(int64_t)c * total + i];
+  red[ph][o] = s;
+  __syncthreads();
+  owner = ph == 0 && i < total;
+  float t = 0.f;
+  if (owner)
+#pragma unroll
+    for (int p = 0; p < 16; ++p) t += red[p][o];
+  return t;
 }
 
 static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }      // workspace sections start on 256 bytes

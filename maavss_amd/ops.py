@@ -314,53 +314,6 @@ def bn_pool_act_bwd(dout, out, arg, y, mean, invstd, gamma, pool, act, strides=N
     return dy
 
 
-# ---------------------------------------------------------------------------------------------- conv2d
-def conv2d_out(h, w, sh, sw, pw):
-    return (h + 2 - 3) // sh + 1, (w + 2 * pw - 9) // sw + 1
-
-
-def conv2d_fwd(x, w, stride, pw, in_nchw):
-    _f32(x, w)
-    co, ci = w.shape[0], w.shape[1]
-    if in_nchw:
-        b, _, h, wd = x.shape
-    else:
-        b, h, wd, _ = x.shape
-    ho, wo = conv2d_out(h, wd, stride[0], stride[1], pw)
-    y = torch.empty(b, ho, wo, co, device=x.device, dtype=torch.float32)
-    call("maavss_conv2d_fwd", ptr(x), ptr(w), ptr(y), b, ci, h, wd, co, stride[0], stride[1], pw, 0 if in_nchw else 1,
-         stream_ptr())
-    return y
-
-
-def conv2d_dgrad(dy, w, in_hw, stride, pw):
-    _f32(dy, w)
-    co, ci = w.shape[0], w.shape[1]
-    b = dy.shape[0]
-    dx = torch.empty(b, in_hw[0], in_hw[1], ci, device=dy.device, dtype=torch.float32)
-    call("maavss_conv2d_dgrad", ptr(dy), ptr(w), ptr(dx), b, ci, in_hw[0], in_hw[1], co, stride[0], stride[1], pw,
-         stream_ptr())
-    return dx
-
-
-def conv2d_wgrad(x, dy, w_shape, stride, pw, in_nchw, dw=None, beta=0):
-    _f32(x, dy, dw)
-    co, ci = w_shape[0], w_shape[1]
-    if in_nchw:
-        b, _, h, wd = x.shape
-    else:
-        b, h, wd, _ = x.shape
-    ho, wo = dy.shape[1], dy.shape[2]
-    nchunk = query("maavss_conv2d_wgrad_nchunk", b, ho, wo, ci, co)
-    ws = torch.empty(nchunk * co * ci * 27, device=x.device, dtype=torch.float32)
-    if dw is None:
-        dw = torch.empty(co, ci, 3, 9, device=x.device, dtype=torch.float32)
-        beta = 0
-    call("maavss_conv2d_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws), b, ci, h, wd, co, stride[0], stride[1], pw,
-         0 if in_nchw else 1, int(beta), stream_ptr())
-    return dw
-
-
 # ---------------------------------------------------------------------------------------------- generic conv2d (K19)
 ACT_LEAKY = 3
 
@@ -402,14 +355,35 @@ def conv_gen_big(small, w, bias, big, stride, pad):
 
 def conv_gen_wgrad(small, big, w_shape, stride, pad, dw=None, beta=0):
     cs, cb, kh, kw = w_shape
-    nchunk = query("maavss_conv2d_gen_wgrad_nchunk", small.b, small.h, small.w)
-    ws = torch.empty(nchunk * cs * cb * kh * kw, device=small.t.device, dtype=torch.float32)
+    assert small.c == cs and big.c == cb
+    geom = (small.b, cs, small.h, small.w, cb, big.h, big.w, kh, kw, stride[0], stride[1], pad[0], pad[1], small.strides, big.strides)
+    ws = _lib.workspace(query("maavss_conv2d_gen_wgrad_ws_bytes", *geom), small.t.device)
     if dw is None:
         dw, beta = torch.empty(cs, cb, kh, kw, device=small.t.device, dtype=torch.float32), 0
-    assert small.c == cs and big.c == cb
-    call("maavss_conv2d_gen_wgrad", ptr(small.t), ptr(big.t), ptr(dw), ptr(ws), small.b, cs, small.h, small.w, cb, big.h, big.w, kh, kw,
-         stride[0], stride[1], pad[0], pad[1], small.strides, big.strides, int(beta), stream_ptr())
+    call("maavss_conv2d_gen_wgrad", ptr(small.t), ptr(big.t), ptr(dw), ptr(ws), *geom, int(beta), stream_ptr())
     return dw
+
+
+# Conv2d(k=(3,9), padding (1,pw), bias=False) of the STFT encoder, on dense tensors: x NCHW (the network input) or NHWC, y / dy / dx NHWC
+def conv2d_out(h, w, sh, sw, pw):
+    return (h + 2 - 3) // sh + 1, (w + 2 * pw - 9) // sw + 1
+
+
+def conv2d_fwd(x, w, stride, pw, in_nchw):
+    xm = Map(x, nchw=in_nchw)
+    y = torch.empty(xm.b, *conv2d_out(xm.h, xm.w, stride[0], stride[1], pw), w.shape[0], device=x.device, dtype=torch.float32)
+    conv_gen_small(xm, w, None, Map(y), stride, (1, pw))
+    return y
+
+
+def conv2d_dgrad(dy, w, in_hw, stride, pw):
+    dx = torch.empty(dy.shape[0], in_hw[0], in_hw[1], w.shape[1], device=dy.device, dtype=torch.float32)
+    conv_gen_big(Map(dy), w, None, Map(dx), stride, (1, pw))
+    return dx
+
+
+def conv2d_wgrad(x, dy, w_shape, stride, pw, in_nchw, dw=None, beta=0):
+    return conv_gen_wgrad(Map(dy), Map(x, nchw=in_nchw), w_shape, stride, (1, pw), dw=dw, beta=beta)
 
 
 # ConvTranspose2d(k=(3,kw), padding (1,4), bias=False) of the STFT decoder, on dense tensors: x / dx NHWC, y / dy NHWC or NCHW

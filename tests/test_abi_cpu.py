@@ -18,7 +18,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(cdll, name), f"{name} declared in include/maavss.h but not exported"
     L = _lib.lib()
     assert L.cdll.maavss_arch() == b"gfx950"
-    assert L.cdll.maavss_version() == _lib.header_abi_version() == 401
+    assert L.cdll.maavss_version() == _lib.header_abi_version() == 402
 
 
 def test_no_cpu_fallback():

@@ -128,7 +128,7 @@ def test_entry_point_is_exported_and_validates_before_touching_the_device():
     from maavss_amd import _lib
     L = _lib.lib()
     assert "maavss_vit_attn_masks" in L.protos and len(L.protos["maavss_vit_attn_masks"][1]) == 12
-    assert _lib.header_abi_version() == 401 and L.cdll.maavss_version() == 401, "the entry point was additive in 400; 401 removed the convt2d entry points"
+    assert _lib.header_abi_version() == 402 and L.cdll.maavss_version() == 402, "the entry point was additive in 400; 401 removed the convt2d, 402 the conv2d entry points"
     good = dict(att=256, out=512, out_dtype=0, n_frames=2, heads=6, H=224, W=224, patch=8, upsample=1, threshold=0.6, flag=None, stream=None)
 
     def call(**kw):

@@ -233,7 +233,7 @@ def test_new_symbols_are_in_the_header_and_the_library_and_the_abi_version_is_st
         assert name in protos and hasattr(L.cdll, name), name
     assert [n for _, n in protos["maavss_bss_eval"][1]] == ["est", "est_stride", "ref", "ref_stride", "others", "others_row_stride",
                                                             "others_src_stride", "K", "rows", "n", "L", "out", "ws", "ws_bytes", "stream"]
-    assert _lib.header_abi_version() == 401 == L.cdll.maavss_version()
+    assert _lib.header_abi_version() == 402 == L.cdll.maavss_version()
 
 
 def test_validator_keys_and_buffer_without_and_with_the_option():

@@ -165,4 +165,4 @@ def test_header_declares_the_window_entry_points():
         ret, args = protos[name]
         assert args[-1][1] == "stream", name
     assert [n for _, n in protos["maavss_av_stitch"][1]][:2] == ["pred", "clip_absmax"]
-    assert _lib.header_abi_version() == 401          # additive in 400; 401 removed the convt2d entry points
+    assert _lib.header_abi_version() == 402          # additive in 400; 401 removed the convt2d, 402 the conv2d entry points

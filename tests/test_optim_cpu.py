@@ -300,7 +300,7 @@ def test_symbols_are_in_the_header_and_the_library_and_the_abi_is_401():
     assert [a for _, a in protos["maavss_adamw_ema_step"][1]] == [
         "p", "g", "m", "v", "ema", "n", "lr", "beta1", "beta2", "eps", "step", "grad_scale", "scale_dev", "norm_dev", "skip_nonfinite",
         "skipped", "count_skip", "host_seg_end", "host_seg_wd", "n_seg", "ema_decay", "stream"]
-    assert _lib.header_abi_version() == 401 == lib.cdll.maavss_version()
+    assert _lib.header_abi_version() == 402 == lib.cdll.maavss_version()
     text = open(_lib.HEADER).read()
     block = text[text.index("EXTENSION: AdamW decay"):text.index("int maavss_adamw_ema_step(")]
     assert "NOT in the reference" in block and "GradScaler" in block

@@ -117,7 +117,7 @@ def test_new_symbols_are_exported_and_the_abi_version_is_still_401():
                  "maavss_spectrum_metrics", "maavss_sqerr_rows_chunk", "maavss_sqerr_rows_ws_bytes", "maavss_sqerr_rows",
                  "maavss_metric_add_sum", "maavss_metric_add_classes"):
         assert name in protos and hasattr(L.cdll, name), name
-    assert _lib.header_abi_version() == 401 == L.cdll.maavss_version()
+    assert _lib.header_abi_version() == 402 == L.cdll.maavss_version()
     sig = inspect.signature(maavss_amd.Validator.__init__).parameters
     assert (sig["loss_coeff"].default, sig["num_seq"].default, sig["seg_len"].default, sig["lsd_floor"].default) == (0.001, 1, 256, 1e-10)
     assert inspect.signature(maavss_amd.wave_metrics).parameters["seg_len"].default == 256

@@ -24,7 +24,7 @@ def _reverb(k=K, rooms=4, **kw):
 def test_exported():
     assert maavss_amd.Reverb is maavss_amd.reverb.Reverb is Reverb
     protos = _lib.parse_header()
-    assert "maavss_reverb" in protos and "maavss_rir_synth" in protos and _lib.header_abi_version() == 401
+    assert "maavss_reverb" in protos and "maavss_rir_synth" in protos and _lib.header_abi_version() == 402
 
 
 # ---- the twin --------------------------------------------------------------------------------------------------------------------------

@@ -190,7 +190,7 @@ def test_new_symbols_are_exported_and_the_abi_version_is_still_401():
     L = _lib.lib()
     for name in ("maavss_spectral_loss_ws_bytes", "maavss_spectral_loss", "maavss_spectral_loss_pair_ws_bytes", "maavss_spectral_loss_pair"):
         assert name in protos and hasattr(L.cdll, name), name
-    assert _lib.header_abi_version() == 401 == L.cdll.maavss_version()
+    assert _lib.header_abi_version() == 402 == L.cdll.maavss_version()
     assert _lib.query("maavss_spectral_loss_ws_bytes", 3, 8) == 512 and _lib.query("maavss_spectral_loss_ws_bytes", 0, 8) == 0
     assert _lib.query("maavss_spectral_loss_pair_ws_bytes", 3, 8) == 512 + 256 + 2048
     assert _lib.query("maavss_spectral_loss_pair_ws_bytes", 3, 0) == 0 and _lib.query("maavss_spectral_loss_ws_bytes", 1 << 20, 1 << 20) == 0

@@ -87,4 +87,4 @@ def test_header_declares_the_transform_entry_points():
     assert {"antialias", "autocontrast", "clip_frames", "S"} <= set(names)
     ret, args = protos["maavss_video_transform_ws_bytes"]
     assert [n for _, n in args] == ["F", "clip_frames", "H0", "W0", "S", "antialias", "autocontrast"]
-    assert _lib.header_abi_version() == 401          # additive in 400; 401 removed the convt2d entry points
+    assert _lib.header_abi_version() == 402          # additive in 400; 401 removed the convt2d, 402 the conv2d entry points
