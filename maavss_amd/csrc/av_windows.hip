@@ -193,7 +193,8 @@ extern "C" int maavss_av_stft_windows(const float* y, int64_t n_clips, int clip_
                    num_seq, clip_rows);
   const int64_t run = (int64_t)hops_per_frame * win_frames * n_bins;
   hipStream_t st = (hipStream_t)stream;
-  if ((hops_per_frame * n_bins) % 4 == 0 && av_aligned16(y) && av_aligned16(out)) {
+  // float4 runs start at ((c * 2 + p) * clip_rows + a j) * n_bins floats of y: every plane and every hop offset must be a multiple of 4
+  if (((int64_t)hops_per_frame * n_bins) % 4 == 0 && ((int64_t)clip_rows * n_bins) % 4 == 0 && av_aligned16(y) && av_aligned16(out)) {
     const int64_t total = n_win * 2 * run / 4;
     hipLaunchKernelGGL(av_stft_windows_kernel<4>, dim3(av_grid(total)), dim3(256), 0, st, y, n_clips, clip_rows, n_bins, hops_per_frame,
                        num_seq, win_frames, w0, out, total);

@@ -100,8 +100,12 @@ __global__ __launch_bounds__(256) void video_transform_tables_kernel(const int32
     start = min((int)real, in - 1);
     count = 2;
     const float l1 = fminf(fmaxf(real - (float)start, 0.f), 1.f);
-    wt[0] = 1.0f - l1;
-    wt[S] = l1;
+    // start == in - 1: the gather clamps the second tap onto the first one's pixel, so the two are one tap of weight 1.  Stored as
+    // (1 - l1, l1) they sum to 1 only within 2^-24, and a one-pixel crop (every coordinate of which is this case) would not resize
+    // to a constant plane: autocontrast would then stretch that rounding noise to [0, 1] instead of taking its max == min branch.
+    const bool last = start >= in - 1;
+    wt[0] = last ? 1.0f : 1.0f - l1;
+    wt[S] = last ? 0.0f : l1;
   }
   int32_t* r = ranges + (((int64_t)clip * 2 + axis) * S + o) * 2;
   r[0] = start;
