@@ -15,6 +15,8 @@ stream (ClipPipeline).
                                                                               # past); dry: the target stays the dry clip (dereverberation)
     python examples/train_synthetic.py --reverb 16 --rooms image --mix 1      # 16 shoebox rooms (image-source model) of 2 sources: a clip and
                                                                               # its partner are heard in the same room
+    python examples/train_synthetic.py --reverb 16 --rooms image --calibrate t20   # the rooms' walls searched until the MEASURED T20 is the
+                                                                              # requested time (Reverb.measure); prints requested against measured
     python examples/train_synthetic.py --clip 1.0 --watch 2                   # gradient-norm clipping; per-tensor histograms every 2 steps
     python examples/train_synthetic.py --val 2                                # every 2 steps: held-out loss and LSD, a checkpoint on improvement
     python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
@@ -72,6 +74,9 @@ def main():
                          "(Reverb.sample_rooms + make_room_rirs); with --mix K every clip and its K partners are sources of one room")
     ap.add_argument("--room_sources", type=int, default=None, metavar="S",
                     help="with --rooms image: source positions per room (default: K + 1 with --mix K, else 1)")
+    ap.add_argument("--calibrate", choices=("t20", "t30", "edt"), default=None,
+                    help="with --rooms image: search every room's wall coefficient until this measured decay time is the requested one "
+                         "(make_room_rirs(calibrate=)); prints requested against measured times of every epoch's rooms")
     ap.add_argument("--reverb_target", choices=("wet", "dry"), default="wet",
                     help="with --reverb: the target is the reverberant clip (wet) or the dry one (dry: not together with --mix)")
     ap.add_argument("--clip", type=float, default=None, metavar="MAX_NORM",
@@ -115,6 +120,8 @@ def main():
         ap.error("--reverb_target dry does not go with --mix: the target of a reverberant mixture is not built")
     if a.rooms == "image" and not a.reverb:
         ap.error("--rooms image chooses how --reverb N fills its table: it goes with --reverb")
+    if a.calibrate and a.rooms != "image":
+        ap.error("--calibrate searches the walls of image-source rooms: it goes with --reverb N --rooms image")
     room_sources = a.room_sources if a.room_sources is not None else a.mix + 1
     if a.rooms == "image" and a.mix and (room_sources < a.mix + 1 or a.batch % (a.mix + 1)):
         ap.error(f"--rooms image with --mix {a.mix}: groups of {a.mix + 1} clips share a room, so --room_sources must be at least {a.mix + 1} "
@@ -153,7 +160,11 @@ def main():
         """The epoch's table: N decaying-noise responses, or N image-source rooms of room_sources sources each."""
         if a.rooms == "image":
             dims, mic, sources, rt60 = reverb.sample_rooms(a.reverb, torch.Generator().manual_seed(seed), sources=room_sources)
-            reverb.make_room_rirs(dims, mic, sources, rt60=rt60)
+            reverb.make_room_rirs(dims, mic, sources, rt60=rt60, calibrate=a.calibrate)
+            if a.calibrate:                                      # set-up, once an epoch: the calibration synchronises once a round
+                pairs = ", ".join(f"{want:.3f}->{got:.3f}{'' if ok else '!'}" for want, got, ok in
+                                  zip(rt60.tolist(), reverb.room_measured.tolist(), reverb.room_converged.tolist()))
+                print(f"[rooms] seed {seed}: requested -> measured {a.calibrate} after {reverb.calibration_rounds} rounds (s): {pairs}", flush=True)
         else:
             reverb.make_rirs(a.reverb, seed=seed)
 

@@ -899,6 +899,35 @@ int maavss_reverb(const float* src, int64_t n_src, const int64_t* start, const i
 int maavss_room_rir(const double* geom, const int32_t* bounds, const double* host_geom, const int32_t* host_bounds, int64_t n_rows,
                     const double* table, int H, int R, double sr, double c, int K, float* rirs, int64_t ld_rir, void* stream);
 
+/* ---- EXTENSION: room-acoustic figures of a response table (maavss_amd.Reverb.measure) ---------------------------------------------
+ * What a stored response IS, whichever way the table was filled: row r of out f64 [n_rows][6] = (energy, edt, t20, t30, c50_db,
+ * drr_db) of h = rirs + r * ld_rir (f32, K taps).  tests/rir_measure_twin.py restates the definition in float64.  Additive symbol
+ * (nothing existing changed meaning).
+ *
+ * Backward energy (the Schroeder integral): E[k] = sum_{j >= k} (double)h[j] * (double)h[j]; every product is exact in f64, so only the
+ * order of the additions matters, and it is ONE order.  The taps form blocks of 32 (block b = taps 32 b .. 32 b + 31, the last one
+ * cut at K):
+ *   s[k] = s[k + 1] + h[k]^2 inside a block, from its last tap towards its first, from +0.0;   T[b] = s[32 b];
+ *   C[B - 1] = +0.0,  C[b] = C[b + 1] + T[b + 1], from the last block towards the first;        E[k] = s[k] + C[k / 32].
+ * energy = E[0].  No atomic; two runs give identical bytes, and a row in a table has the bytes of a table of its own.
+ * Crossing of level l in (-5, -10, -25, -35) dB with threshold c_l = thresholds[l] (host memory, n_thresholds = 4; the caller forms
+ * 10^(l / 10) in f64, so no device pow enters a decision; they must descend inside (0, 1)): the first j >= 1 with
+ * E[j] <= E[0] * c_l, a plain f64 comparison.  Its time in samples:
+ *   t_l = (double)(j - 1) + (d[j - 1] - l) / (d[j - 1] - d[j]),   d[i] = 10.0 * log10(E[i] / E[0])
+ * (IEEE decides what E[j] = 0 gives: d[j] = -inf, t_l = j - 1); NaN when no tap crosses.
+ *   edt = (6.0 * t_-10) / sr,   t20 = (3.0 * (t_-25 - t_-5)) / sr,   t30 = (2.0 * (t_-35 - t_-5)) / sr      seconds.
+ * Early and late energy at a boundary tap kb: late = E[kb], +0.0 when kb >= K; early = the sum over k < kb in a forward order of its
+ * own (NOT E[0] - E[kb], which rounds where the direct path alone is exact): per block f[b] = the squares of its taps below kb, first
+ * tap towards last, from +0.0; early = ((f[0] + f[1]) + f[2]) + ..., from +0.0, over the blocks that hold a tap below kb.
+ *   c50_db = 10.0 * log10(early / late) at kb = k_early (the caller's round(0.050 sr)),   drr_db the same at kb = k_direct.
+ * An all-zero row gives energy 0 and NaN elsewhere; a non-finite tap makes its own row's figures what IEEE gives and touches no other
+ * row.  log10 is the device library's (1 ulp): tests/rir_measure_twin.py derives what that allows a figure to differ from the twin's.
+ * 1 <= K <= 32768, 1 <= n_rows <= 2^19, ld_rir >= K, k_direct, k_early >= 0; rirs 4-byte aligned, out 8-byte, contiguous.  No
+ * allocation, no workspace, no synchronisation.  One launch on `stream`: a workgroup per row, the row staged through LDS 8192 taps at
+ * a time (twice: totals, then crossings). */
+int maavss_rir_measure(const float* rirs, int64_t n_rows, int K, int64_t ld_rir, double sr, int k_direct, int k_early,
+                       const double* thresholds, int n_thresholds, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

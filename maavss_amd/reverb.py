@@ -15,6 +15,7 @@ make_room_rirs fills the same table from geometry instead: the image-source mode
 (maavss_room_rir, csrc/room_rir.hip; tests/room_twin.py restates the definition in float64 and the kernel gives its bytes).  Row
 room * S + j is source j of a room, so clips that are given rows of one room (sample_room_index) are sources heard in the same walls.
 """
+import ctypes
 import math
 
 import torch
@@ -23,6 +24,72 @@ from . import _lib
 from ._lib import call, ptr, stream_ptr
 
 TARGETS = ("wet", "dry")
+FIGURES = ("energy", "edt", "t20", "t30", "c50_db", "drr_db")      # the columns of maavss_rir_measure's output
+LEVELS_DB = (-5.0, -10.0, -25.0, -35.0)                            # the Schroeder levels the decay times are read at
+# per decay figure: the lower level it is read at, in dB below the start (calibration sizes its scratch table by it)
+CALIBRATE = {"t20": 25.0, "t30": 35.0, "edt": 10.0}
+
+
+def thresholds():
+    """The energy thresholds 10^(level / 10) of LEVELS_DB as Python floats: what maavss_rir_measure compares E[j] / E[0] against."""
+    return tuple(10.0 ** (level / 10.0) for level in LEVELS_DB)
+
+
+class Calibration:
+    """The search behind make_room_rirs(calibrate=): per room, the uniform wall coefficient whose measured decay time is `target`.
+    Host arithmetic only (CPU f64 tensors): the caller measures, `update` moves.  The unknown is x = -1 / ln(beta), which Eyring's
+    formula makes the decay time proportional to.  A round: T = the measured time at beta(); a room within tol (relative) of its
+    target is done and keeps that coefficient; any other room records its bracket (the largest x seen with T below target, the
+    smallest with T above; a NaN, the level not reached inside the measured taps, counts as above) and moves to x target / T, or,
+    once both bracket ends exist and that step falls outside them (or T is NaN), to the bracket's midpoint (half of x while there is
+    no lower end).  The decay time of an image-source room is not smooth in beta, the plain multiplicative step oscillates in some
+    rooms; the bracket makes it settle."""
+
+    def __init__(self, beta0, target, tol):
+        self.target = torch.as_tensor(target, dtype=torch.float64).reshape(-1).clone()
+        b = torch.as_tensor(beta0, dtype=torch.float64).reshape(-1).clamp(1e-12, 1.0 - 2.0 ** -40)
+        self.x = -1.0 / torch.log(b)
+        n = self.x.numel()
+        self.tol = float(tol)
+        self.lo, self.hi = torch.zeros(n, dtype=torch.float64), torch.full((n,), math.inf, dtype=torch.float64)
+        self.converged = torch.zeros(n, dtype=torch.bool)
+        self.best_x, self.best_t = self.x.clone(), torch.full((n,), math.nan, dtype=torch.float64)
+        self.best_err = torch.full((n,), math.inf, dtype=torch.float64)
+        self.rounds = 0
+
+    @staticmethod
+    def beta_of(x):
+        return torch.exp(-1.0 / x)
+
+    def beta(self):
+        """The coefficients to measure next, f64 [n]: the kept one for a room that is done."""
+        return self.beta_of(torch.where(self.converged, self.best_x, self.x))
+
+    def update(self, measured):
+        """measured f64 [n]: the figure of every room at beta() -> True when every room is done."""
+        t = torch.as_tensor(measured, dtype=torch.float64).reshape(-1)
+        self.rounds += 1
+        for r in range(self.x.numel()):
+            if bool(self.converged[r]):
+                continue
+            x, tr, goal = float(self.x[r]), float(t[r]), float(self.target[r])
+            err = abs(tr - goal) / goal if math.isfinite(tr) else math.inf
+            if err < float(self.best_err[r]) or self.rounds == 1:
+                self.best_x[r], self.best_t[r], self.best_err[r] = x, tr, err
+            if err <= self.tol:
+                self.converged[r] = True
+                continue
+            if math.isfinite(tr) and tr < goal:
+                self.lo[r] = max(float(self.lo[r]), x)
+            else:
+                self.hi[r] = min(float(self.hi[r]), x)
+            lo, hi = float(self.lo[r]), float(self.hi[r])
+            step = x * goal / tr if math.isfinite(tr) and tr > 0.0 else math.nan
+            if lo > 0.0 and math.isfinite(hi):
+                self.x[r] = step if lo < step < hi else 0.5 * (lo + hi)
+            else:
+                self.x[r] = step if math.isfinite(step) else 0.5 * x
+        return bool(self.converged.all())
 
 
 def _range(name, v, positive=False):
@@ -74,6 +141,8 @@ class Reverb:
         self.device = torch.device(device)
         self.rirs = None                      # the current table [n, K] on the device, what make_rirs / make_room_rirs made last
         self.sources_per_room = None          # S when make_room_rirs made the table (row room * S + j), None for make_rirs' rooms
+        # what make_room_rirs(calibrate=) found (CPU): beta f64 [n, 6], the measured figure f64 [n], converged bool [n], rounds run
+        self.room_beta = self.room_measured = self.room_converged = self.calibration_rounds = None
 
     # ---- host logic: draws and refusals, no device work ---------------------------------------------------
     def sample(self, n, generator):
@@ -129,7 +198,9 @@ class Reverb:
         walls, clamped into [0, 1]: Eyring's formula (rt60 = 0.161 V / (-A_surf ln(1 - alpha)), beta^2 = 1 - alpha) solved for beta.
         This is a NOMINAL figure.  An image-source shoebox with uniform walls decays more slowly than Eyring predicts, because the
         axial paths graze fewer walls than a diffuse field does: a CPU prototype of the definition measured T20 of 0.46, 0.85 and
-        0.37 s for nominal 0.30, 0.50 and 0.25 s in three rooms (profiles/room_rir_decay.json holds the float64 twin's ratios)."""
+        0.37 s for nominal 0.30, 0.50 and 0.25 s in three rooms (profiles/room_rir_decay.json holds the float64 twin's ratios).
+        make_room_rirs(rt60=, calibrate="t20") starts from this figure and searches the coefficient whose MEASURED decay time
+        (Reverb.measure) is the one requested."""
         d = torch.as_tensor(dims, dtype=torch.float64).reshape(-1, 3)
         rt = torch.as_tensor(rt60, dtype=torch.float64).reshape(-1)
         if rt.numel() not in (1, d.shape[0]):
@@ -174,10 +245,12 @@ class Reverb:
             src[bad] = margin + span[room] * torch.rand(int(bad.sum()), 3, generator=generator, dtype=torch.float64)
         raise ValueError(f"min_distance = {dist} leaves sources too close to the microphone after 64 redraws: the rooms are too small for it")
 
-    def check_rooms(self, dims, mic, sources, beta=None, rt60=None, c=343.0, half_width=8, resolution=32):
+    def check_rooms(self, dims, mic, sources, beta=None, rt60=None, c=343.0, half_width=8, resolution=32, taps=None):
         """Every refusal of make_room_rirs, from values alone (no device work) -> (geom f64 [n S, 15] = (L, m, s, beta) per row,
         bounds int32 [n S, 3], table f64 [2 H R + 1], S).  The lattice bounds: N_a = floor(Rmax / (2 L_a)) + 1 with
-        Rmax = d0 + (K + H) c / sr, beyond which no image reaches a tap below K."""
+        Rmax = d0 + (K + H) c / sr, beyond which no image reaches a tap below K.  K is rir_len, or `taps` when given (the scratch
+        table a calibration measures)."""
+        k_taps = self.rir_len if taps is None else taps
         table = self.kernel_table(half_width, resolution)
         if isinstance(c, bool) or not isinstance(c, (int, float)) or not (math.isfinite(c) and c > 0):
             raise ValueError(f"c must be a positive number (m/s), got {c!r}")
@@ -222,12 +295,12 @@ class Reverb:
         d0 = ((diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]).sqrt()         # [n, S]
         if not bool((d0 > 0).all()):
             raise ValueError("a source lies on its microphone")
-        rmax = d0 + (self.rir_len + half_width) * float(c) / float(self.sr)
+        rmax = d0 + (k_taps + half_width) * float(c) / float(self.sr)
         bounds = torch.floor(rmax[..., None] / (2.0 * d[:, None, :])) + 1.0                                            # [n, S, 3]
         images = 8.0 * (2.0 * bounds + 1.0).prod(dim=2)
         if not bool((images <= float(1 << 31)).all()):
             r = int((images > float(1 << 31)).nonzero()[0, 0])
-            raise ValueError(f"room {r} ({d[r].tolist()} m) needs a lattice box of {images[r].max().item():.3g} images for {self.rir_len} taps, "
+            raise ValueError(f"room {r} ({d[r].tolist()} m) needs a lattice box of {images[r].max().item():.3g} images for {k_taps} taps, "
                              f"above the cap of 2^31")
         geom = torch.cat([d[:, None, :].expand(n, s, 3), m[:, None, :].expand(n, s, 3), src, b[:, None, :].expand(n, s, 6)], dim=2)
         return geom.reshape(n * s, 15).contiguous(), bounds.to(torch.int32).reshape(n * s, 3).contiguous(), table, s
@@ -326,32 +399,138 @@ class Reverb:
         self.rirs, self.sources_per_room = rirs, None
         return rirs
 
-    def make_room_rirs(self, dims, mic, sources, *, beta=None, rt60=None, c=343.0, half_width=8, resolution=32):
+    def check_measure(self, rirs=None, direct_ms=2.5):
+        """Every refusal of measure, from shapes, dtypes and values alone (no device work) -> (rirs, k_direct, k_early)."""
+        if isinstance(direct_ms, bool) or not isinstance(direct_ms, (int, float)) or not (math.isfinite(direct_ms) and direct_ms >= 0):
+            raise ValueError(f"direct_ms must be a finite non-negative number, got {direct_ms!r}")
+        if rirs is None:
+            if self.rirs is None:
+                raise ValueError("no room responses yet: call make_rirs or make_room_rirs first, or pass rirs")
+            rirs = self.rirs
+        if not isinstance(rirs, torch.Tensor) or rirs.dtype != torch.float32:
+            raise ValueError(f"rirs must be a float32 tensor, got {getattr(rirs, 'dtype', type(rirs))}")
+        if rirs.dim() != 2 or rirs.shape[0] < 1 or rirs.shape[1] < 1:
+            raise ValueError(f"rirs must be [n, K] with n, K >= 1, got {tuple(rirs.shape)}")
+        n, k = rirs.shape
+        if k > 32768 or n > 1 << 19:
+            raise ValueError(f"a table holds at most {1 << 19} responses of at most 32768 taps, got {(n, k)}")
+        if (k > 1 and rirs.stride(1) != 1) or (n > 1 and rirs.stride(0) < k):
+            raise ValueError(f"rirs must have unit last stride and a row stride of at least K = {k}, got strides {rirs.stride()}")
+        a, b = rirs.device, self.device                     # "cuda" names the current device: it goes with any index
+        if a.type != b.type or (a.index is not None and b.index is not None and a.index != b.index):
+            raise ValueError(f"rirs is on {rirs.device}, this Reverb on {self.device}")
+        k_direct = math.floor(direct_ms * self.sr / 1000.0) + 1
+        k_early = round(0.050 * self.sr)
+        if k_direct >= 1 << 30 or k_early >= 1 << 30:
+            raise ValueError(f"direct_ms = {direct_ms!r} at sr = {self.sr!r} is no tap index")
+        return rirs, k_direct, k_early
+
+    def measure(self, rirs=None, *, direct_ms=2.5):
+        """The room-acoustic figures of a response table (by default the current one, `reverb.rirs`; any float32 [n, K] with unit last
+        stride on this device otherwise) -> a dict of device f64 tensors [n] (columns of one [n, 6] buffer):
+            energy   E[0], the sum of the squared taps                   edt      6 x the time the Schroeder curve takes to -10 dB
+            t20      3 x its time from -5 to -25 dB                      t30      2 x its time from -5 to -35 dB        (seconds)
+            c50_db   10 log10 of the energy in front of tap round(0.050 sr) over the energy from it on
+            drr_db   the same at tap floor(direct_ms sr / 1000) + 1: direct_ms = 0 sets tap 0 alone against everything behind it
+        A decay time is NaN when the row never falls to its lower level, every figure but energy is NaN for a silent row, and a
+        non-finite tap spoils its own row only (maavss_rir_measure, include/maavss.h; tests/rir_measure_twin.py restates the
+        definition in float64: energies and crossings bit for bit, times and dB within a few ulp of log10).  Everything is checked
+        before any device work; one launch on the current stream, no workspace, no synchronisation."""
+        rirs, k_direct, k_early = self.check_measure(rirs, direct_ms)
+        _lib.require_cuda(rirs)
+        n, k = rirs.shape
+        out = torch.empty(n, len(FIGURES), device=rirs.device, dtype=torch.float64)
+        levels = (ctypes.c_double * len(LEVELS_DB))(*thresholds())
+        call("maavss_rir_measure", ptr(rirs), n, k, rirs.stride(0) if n > 1 else k, float(self.sr), k_direct, k_early,
+             ctypes.addressof(levels), len(LEVELS_DB), ptr(out), stream_ptr())
+        return {name: out[:, i] for i, name in enumerate(FIGURES)}
+
+    def check_calibration(self, dims, rt60, beta, calibrate, tol, max_iter, measure_len):
+        """Every refusal of make_room_rirs' calibration arguments (no device work) -> the scratch table's taps.  By default the
+        smallest multiple of 1024 that holds (lower level + 20 dB) / 60 of the longest requested decay, so that the cut does not
+        bend the Schroeder curve at the level the figure is read at; independent of rir_len."""
+        if calibrate not in CALIBRATE:
+            raise ValueError(f"calibrate must be None or one of {sorted(CALIBRATE)}, got {calibrate!r}")
+        if beta is not None or rt60 is None:
+            raise ValueError("calibrate searches the wall coefficient for a requested rt60: give rt60 and no beta")
+        if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not (math.isfinite(tol) and 0.0 < tol < 1.0):
+            raise ValueError(f"tol must be a relative tolerance in (0, 1), got {tol!r}")
+        _positive_int("max_iter", max_iter)
+        if measure_len is None:
+            if isinstance(rt60, torch.Tensor) and rt60.is_cuda:
+                raise ValueError("rt60 must be a CPU tensor or a number (its values are checked on the host)")
+            rt = torch.as_tensor(rt60, dtype=torch.float64).reshape(-1)
+            if rt.numel() < 1 or not bool((torch.isfinite(rt) & (rt > 0)).all()):
+                raise ValueError("dims and rt60 must be finite and positive")
+            frac = (CALIBRATE[calibrate] + 20.0) / 60.0
+            measure_len = max(1, math.ceil(frac * float(rt.max()) * self.sr / 1024.0)) * 1024
+        else:
+            _positive_int("measure_len", measure_len)
+        if measure_len > 32768:
+            raise ValueError(f"the calibration would measure {measure_len} taps, a table holds at most 32768: pass a shorter measure_len")
+        return measure_len
+
+    def make_room_rirs(self, dims, mic, sources, *, beta=None, rt60=None, c=343.0, half_width=8, resolution=32, calibrate=None, tol=0.02,
+                       max_iter=12, measure_len=None):
         """A table of image-source responses [n S, K] on the device, kept as `reverb.rirs` and returned; row room * S + j is source j
         of a room and `reverb.sources_per_room` = S.  dims [n, 3], mic [n, 3], sources [n, S, 3]: CPU tensors or nested lists, metres,
         positions strictly inside the room.  Exactly one of beta [n, 6] (pressure reflection coefficients of the walls x0 x1 y0 y1 z0
         z1, in [0, 1]) and rt60 [n] (seconds: eyring_beta's nominal figure on all six walls).  c: speed of sound; half_width H and
         resolution R: the fractional-delay kernel (kernel_table).  Every response is normalised to its direct path, which sits at
         lag 0.  Everything is checked before any device work; kernel table, geometry and lattice bounds reach the device in one
-        non-blocking copy from pinned memory; one launch on the current stream, no synchronisation."""
+        non-blocking copy from pinned memory; one launch on the current stream, no synchronisation.
+
+        calibrate = "t20" | "t30" | "edt" (with rt60, never with beta) makes rt60 mean that measured figure: per room, the uniform
+        wall coefficient is searched (Calibration: from eyring_beta, in x = -1 / ln(beta)) until the figure, averaged over the
+        room's S sources, is within `tol` (relative) of the request, at most `max_iter` rounds.  A round fills a scratch table of
+        `measure_len` taps for all rooms, measures it and copies ONE column [n S] f64 to the host: calibration synchronises once a
+        round; it is table set-up, not a training step.  The table itself is then filled by the path above from the coefficients
+        found: `reverb.rirs` has the bytes of make_room_rirs(beta=reverb.room_beta).  reverb.room_beta [n, 6], room_measured [n]
+        (the figure at that coefficient, over measure_len taps), room_converged [n] and calibration_rounds say what was found; a
+        room that is not within tol after max_iter rounds (or whose scratch rows never reach the level: NaN) keeps its best
+        coefficient and is flagged False there, it does not raise."""
+        if calibrate is not None:
+            return self._calibrated_rooms(dims, mic, sources, beta, rt60, c, half_width, resolution, calibrate, tol, max_iter, measure_len)
         geom, bounds, table, s = self.check_rooms(dims, mic, sources, beta, rt60, c, half_width, resolution)
         rirs = torch.empty(geom.shape[0], self.rir_len, device=self.device, dtype=torch.float32)
         self._fill_rooms(geom, bounds, table, half_width, resolution, c, rirs)
         self.rirs, self.sources_per_room = rirs, s
         return rirs
 
+    def _calibrated_rooms(self, dims, mic, sources, beta, rt60, c, half_width, resolution, calibrate, tol, max_iter, measure_len):
+        """make_room_rirs(calibrate=): every refusal (the final table's and the scratch table's) before any device work, then the
+        rounds, then the final table through make_room_rirs(beta=)."""
+        taps = self.check_calibration(dims, rt60, beta, calibrate, tol, max_iter, measure_len)
+        self.check_rooms(dims, mic, sources, None, rt60, c, half_width, resolution)                         # the final table's lattice boxes
+        geom, bounds, table, s = self.check_rooms(dims, mic, sources, None, rt60, c, half_width, resolution, taps=taps)
+        n = geom.shape[0] // s
+        target = torch.as_tensor(rt60, dtype=torch.float64).reshape(-1).expand(n)
+        search = Calibration(geom.reshape(n, s, 15)[:, 0, 9], target, tol)
+        scratch = torch.empty(n * s, taps, device=self.device, dtype=torch.float32)
+        geom = geom.clone()
+        for _ in range(max_iter):
+            geom.reshape(n, s, 15)[:, :, 9:] = search.beta()[:, None, None]
+            self._fill_rooms(geom, bounds, table, half_width, resolution, c, scratch)
+            figure = self.measure(scratch)[calibrate].cpu()                                                  # the round's one host copy
+            if search.update(figure.reshape(n, s).mean(dim=1)):
+                break
+        self.room_beta = Calibration.beta_of(search.best_x)[:, None].expand(n, 6).contiguous()
+        self.room_measured, self.room_converged, self.calibration_rounds = search.best_t.clone(), search.converged.clone(), search.rounds
+        return self.make_room_rirs(dims, mic, sources, beta=self.room_beta, c=c, half_width=half_width, resolution=resolution)
+
     def _fill_rooms(self, geom, bounds, table, half_width, resolution, c, rirs):
-        """The launch behind make_room_rirs: check_rooms' CPU tables into rirs [rows, K] (unit last stride).  Table, geometry and
-        bounds travel as one f64 block (the int32 bounds last, two to a slot); the entry point checks the pinned copy."""
+        """The launch behind make_room_rirs: check_rooms' CPU tables into rirs [rows, K] (unit last stride; K = rir_len, or the
+        taps of a calibration's scratch table).  Table, geometry and bounds travel as one f64 block (the int32 bounds last, two to a
+        slot); the entry point checks the pinned copy."""
         _lib.require_cuda(rirs)
-        rows, n_tab = geom.shape[0], table.numel()
+        rows, n_tab, k_taps = geom.shape[0], table.numel(), rirs.shape[1]
         packed = torch.zeros((3 * rows + 1) // 2 * 2, dtype=torch.int32)
         packed[:3 * rows] = bounds.reshape(-1)
         host = torch.cat([table, geom.reshape(-1), packed.view(torch.float64)]).pin_memory()
         staged = torch.empty(host.numel(), device=self.device, dtype=torch.float64)
         staged.copy_(host, non_blocking=True)
         call("maavss_room_rir", ptr(staged[n_tab:]), ptr(staged[n_tab + 15 * rows:]), ptr(host[n_tab:]), ptr(host[n_tab + 15 * rows:]), rows,
-             ptr(staged), half_width, resolution, float(self.sr), float(c), self.rir_len, ptr(rirs), rirs.stride(0) if rows > 1 else self.rir_len,
+             ptr(staged), half_width, resolution, float(self.sr), float(c), k_taps, ptr(rirs), rirs.stride(0) if rows > 1 else k_taps,
              stream_ptr())
 
     def _convolve(self, src_ptr, n_src, start, floor, index, length, out):
