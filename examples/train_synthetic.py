@@ -22,6 +22,9 @@ stream (ClipPipeline).
     python examples/train_synthetic.py --val 2 --mix 1                        # also BSS-eval SDR / SIR / SAR of the held-out mixtures
     python examples/train_synthetic.py --bank 8 [--bank_storage u16]          # the ViT once per recording: maps and audio of 8 recordings in
                                                                               # HBM (ClipBank), every batch cut from them by clip index
+    python examples/train_synthetic.py --bank 8 --bank_crop [--bank_flip 0.5] # a new random crop (and mirror image) of every clip's stored
+                                                                              # maps in every step (maavss_amd.BankCrop): the map is cropped,
+                                                                              # not the frame -- the ViT still runs once per recording
     python examples/train_synthetic.py --bank 8 --select [--val 2]            # every recording gets a silent and a frozen stretch; the bank's
                                                                               # activity pass finds them and maavss_amd.ClipSampler draws the
                                                                               # epochs from the clips that are left (held-out recordings: --val)
@@ -90,6 +93,10 @@ def main():
                     help="bank R synthetic recordings of 4 clips once (ViT + audio, maavss_amd.ClipBank: the reference's attn_frames_path / "
                          "use_audio_memmap), then draw every batch by clip index from a seeded permutation: no ViT in the step")
     ap.add_argument("--bank_storage", choices=("f32", "u16"), default="f32", help="with --bank: 4 or 2 bytes per map value")
+    ap.add_argument("--bank_crop", action="store_true",
+                    help="with --bank: cut every training clip through a fresh RandomResizedCrop box applied to its stored attention maps "
+                         "(maavss_amd.BankCrop, ClipBank.batch(boxes=)); the held-out batch of --val keeps the whole frame")
+    ap.add_argument("--bank_flip", type=float, default=0.0, metavar="P", help="with --bank_crop: mirror a clip's maps with probability P")
     ap.add_argument("--select", action="store_true",
                     help="with --bank: silence the first clip of every recording and freeze the frames of its last one, reject such clips by the "
                          "bank's activity statistics and iterate maavss_amd.ClipSampler's epochs instead of a hand-drawn permutation")
@@ -114,6 +121,10 @@ def main():
     a = ap.parse_args()
     if a.select and not a.bank:
         ap.error("--select chooses among the clips of a bank: it goes with --bank")
+    if a.bank_crop and not a.bank:
+        ap.error("--bank_crop crops the maps of a bank: it goes with --bank")
+    if a.bank_flip and not a.bank_crop:
+        ap.error("--bank_flip is drawn with the crops: it goes with --bank_crop")
     if a.bank and (a.raw_video or a.raw_audio or a.overfit):
         ap.error("--bank holds transformed frames' maps and 16 kHz audio: it does not go with --raw_video, --raw_audio or --overfit")
     if a.reverb and a.reverb_target == "dry" and a.mix:
@@ -235,7 +246,11 @@ def main():
             ap.error(f"--bank {a.bank} holds {n_train} clips, fewer than one batch of {b}")
         print(f"bank: {len(bank)} clips of {n_rec} recordings, {bank.maps.numel() * bank.maps.element_size() / 1e6:.2f} MB of maps "
               f"({a.bank_storage}), {bank.audio.numel() * 4 / 1e6:.2f} MB of audio", flush=True)
-        pipe = maavss_amd.ClipPipeline(None, stft, clip_frames=t_total, bank=bank, mixer=mixer, reverb=reverb, reverb_target=a.reverb_target)
+        bank_crop = maavss_amd.BankCrop(flip=a.bank_flip) if a.bank_crop else None
+        pipe = maavss_amd.ClipPipeline(None, stft, clip_frames=t_total, bank=bank, mixer=mixer, reverb=reverb, reverb_target=a.reverb_target,
+                                       bank_crop=bank_crop)
+        # the held-out batch is not augmented: the whole frame, nobody mirrored (the extractor's maps come back as they are stored)
+        uncropped = dict(boxes=torch.tensor([[0, 0, w, w]] * b, dtype=torch.int32), flip=torch.zeros(b, dtype=torch.bool)) if a.bank_crop else {}
         g_order, order = torch.Generator().manual_seed(0), []
         if a.select:
             # one pass over the bank on the device (ClipBank.activity), the thresholds there too, one copy of a byte per clip back
@@ -278,9 +293,9 @@ def main():
         if a.select:
             held = maavss_amd.ClipSampler(bank, b, recordings=range(a.bank, n_rec), shuffle=False, **limits)      # the split by file
             print(f"select: {held.accepted.numel()} of {held.n_considered} held-out clips accepted", flush=True)
-            pipe.submit_clips(next(held.epoch(0)), seed=12345, **room_kw(12345))
+            pipe.submit_clips(next(held.epoch(0)), seed=12345, **uncropped, **room_kw(12345))
         elif a.bank:
-            pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345, **room_kw(12345))
+            pipe.submit_clips(list(range(n_train, n_train + b)), seed=12345, **uncropped, **room_kw(12345))
         else:
             g_train, g = g, torch.Generator().manual_seed(12345)
             frames_v, audio_v = batch()

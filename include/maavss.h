@@ -721,6 +721,33 @@ int maavss_bank_attn_clips(const void* maps, int storage, const int32_t* clip_st
  * (the source rows start anywhere and are read as dwords), element stores otherwise.  out must not overlap the bank. */
 int maavss_bank_audio_clips(const float* bank, int64_t n_samples, const int64_t* clip_start, int64_t n_clips, int64_t L, float* out,
                             int64_t ld_out, void* stream);
+/* Per-clip random resized crop and flip of the stored maps, at patch resolution (maavss_amd.ClipBank.batch(boxes=, flip=), warp_maps;
+ * csrc/bank_warp.hip; tests/bank_warp_twin.py restates every operation).  A crop of the attention map is not the attention of the
+ * cropped frame (the ViT would re-attend): this is a geometric augmentation of the tensor the fusion network reads.
+ * Inputs.  S % 8 == 0, hp = S / 8, n = hp * hp.  Per clip b: clip_start[b] as above; boxes[b] = (top, left, height, width), device int32
+ * [n_clips][4], in pixels of the S x S frame, 0 <= top, 1 <= height, top + height <= S and likewise for the columns (the layout of
+ * VideoTransform.sample_boxes; the caller checks its host copy, the kernel clamps what it reads into those bounds); flips[b], device
+ * uint8 [n_clips], non-zero = mirror the columns (flips null: no clip is flipped).
+ * Resampling.  Output patch row i of a clip reads source patch rows a and b, all in integers:
+ *     D = 16 hp,  N = 2 top hp + (2 i + 1) height - 8 hp,  y0 = floor(N / D),  r = N - y0 D  (in [0, D)),
+ *     wy = (double)r / (double)D  (one f64 division),  lo = top / 8,  hi = (top + height - 1) / 8,
+ *     a = clamp(y0, lo, hi),  b = clamp(y0 + 1, lo, hi)
+ * -- N / D is the centre of output patch i in crop coordinates, in source-patch units: bilinear with align_corners = False, clamped to
+ * the patches the box touches.  Columns likewise from left / width: c, d, wx.  With m the stored map of the clip's frame t (storage 0:
+ * f32; 1: the correctly rounded f32 quotient q / 65535), converted exactly to f64:
+ *     r0 = (1 - wx) * m[a][c] + wx * m[a][d],   r1 = (1 - wx) * m[b][c] + wx * m[b][d],   v = (float)((1 - wy) * r0 + wy * r1)
+ * every f64 operation rounded on its own, v rounded once to f32.  A flipped clip writes v to column hp - 1 - j instead of j.
+ * The whole-frame box gives wy = wx = 0 and v = m exactly, flip alone the mirrored map exactly (finite maps).
+ * Frame normalisation (frame_norm != 0), the arithmetic of maavss_vit_attn_maps_pass1: mx = fmaxf over the frame's n values v from
+ * -1e30f, rcp = 1.f / mx, the value stored is v * rcp in f32; frame_norm = 0 stores v.  There is no guard: a frame that is all zero
+ * inside the box gives 0 * inf = NaN, as an all-zero map does in the extractor.
+ * out [n_clips * clip_frames][n] f32, frame t of clip b at row b * clip_frames + t: the maps maavss_bank_attn_clips then reads with
+ * storage = 0 and clip_start[b] = b * clip_frames (clip maximum, attn_diff and the x8 stores are that entry point's, unchanged).
+ * One launch, one workgroup per (clip, frame); no atomics, no float sum: two runs give identical bytes, and a clip's rows do not depend
+ * on the other clips of the call.  A clip reads only its own clip_frames frames.  n_clips * clip_frames must stay below 2^31.
+ * Additive symbol (nothing existing changed meaning). */
+int maavss_bank_warp_maps(const void* maps, int storage, const int32_t* clip_start, const int32_t* boxes, const void* flips,
+                          int64_t n_clips, int64_t n_frames_total, int clip_frames, int S, int frame_norm, float* out, void* stream);
 
 /* ---- EXTENSION: per-clip activity statistics of the clip bank (maavss_amd.ClipBank.activity, maavss_amd.ClipSampler) ------------
  * Which clips of a bank are silent, still or cut (the reference's to_do.txt: "audio thresholding", "video reject"), from one read of

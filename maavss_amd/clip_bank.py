@@ -22,6 +22,9 @@ and the quotient) before the clip normalisation, in half the bytes.
 A clip never reads a map or a sample of a neighbouring recording, with attn_diff too (clip frame 0 is 0 * (1 / m)).
 tests/bank_twin.py restates the pack and the index on the host.
 
+`batch(indices, boxes=, flip=)` crops and mirrors the stored maps per clip on the way out (maavss_bank_warp_maps, csrc/bank_warp.hip;
+tests/bank_warp_twin.py restates it): the bank path's stand-in for the frames-fed path's RandomResizedCrop, drawn by `BankCrop`.
+
 `activity()` is one pass over the bank that says which clips are silent, still or cut (csrc/clip_select.hip; tests/select_twin.py);
 maavss_amd.ClipSampler turns it into the clips an epoch trains on.
 """
@@ -33,6 +36,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream_ptr
+from .video_transform import VideoTransform
 
 FORMAT = "maavss_amd.ClipBank"
 FORMAT_VERSION = 1
@@ -160,7 +164,8 @@ class ClipBank:
             read once at the end (this call may synchronise); a non-finite map raises MaavssError and the recording is not added.
           maps [N,(S//8)^2] f32 as pass 1 writes them: for callers with maps of their own.  They are stored as given, unchecked.
         The crop is whatever the frames were given with: one crop per recording, fixed when it is banked, as in the reference's
-        attention-frame cache.  Frames and samples behind the recording's last whole clip are not kept."""
+        attention-frame cache; batch(boxes=, flip=) crops and mirrors the stored maps per clip and step instead (the map, not the frame:
+        see there).  Frames and samples behind the recording's last whole clip are not kept."""
         n_clips, used_f, used_s = self._check_recording(audio, frames, maps, video_attention)
         u16 = self.storage == "u16"
         if u16 or frames is not None:
@@ -232,16 +237,95 @@ class ClipBank:
         k = idx - firsts[r]
         return (frame0[r] + k * self.frame_hop).to(torch.int32), sample0[r] + s_k[k]
 
-    def batch(self, indices, *, attn_diff=False, out=None):
+    def check_warp(self, b, boxes, flip, frame_norm=True):
+        """Host-side validation of batch()'s crop arguments (no device work) -> None without boxes and flip, else (boxes CPU int32
+        [b, 4], flip CPU uint8 [b]): a missing box is the whole frame, a missing flip none."""
+        if boxes is None and flip is None:
+            if frame_norm is not True:
+                raise ValueError("frame_norm= belongs to the warped path: it needs boxes= or flip=")
+            return None
+        s = self.frame_size
+        if s % 8:
+            raise ValueError(f"boxes= / flip= resample the {s // 8} x {s // 8} patch grid and need frame_size % 8 == 0, got {s}")
+        if boxes is None:
+            boxes = torch.tensor([0, 0, s, s], dtype=torch.int32).repeat(b, 1)
+        else:
+            if not isinstance(boxes, torch.Tensor) or boxes.device.type != "cpu" or boxes.dtype != torch.int32 or tuple(boxes.shape) != (b, 4):
+                raise ValueError(f"boxes must be a CPU int32 tensor [{b}, 4] of (top, left, height, width), one per clip, got "
+                                 f"{getattr(boxes, 'dtype', type(boxes))} {tuple(getattr(boxes, 'shape', ()))}"
+                                 f"{' on ' + str(boxes.device) if isinstance(boxes, torch.Tensor) and boxes.device.type != 'cpu' else ''}")
+            top, left, h, w = boxes.to(torch.int64).unbind(1)
+            bad = (h < 1) | (w < 1) | (top < 0) | (left < 0) | (top + h > s) | (left + w > s)
+            if bool(bad.any()):
+                k = int(bad.nonzero()[0, 0])
+                raise ValueError(f"box {k} = {tuple(boxes[k].tolist())} (top, left, height, width) is empty or not inside the {s}x{s} frame")
+            boxes = boxes.contiguous()
+        if flip is None:
+            flip = torch.zeros(b, dtype=torch.uint8)
+        else:
+            if (not isinstance(flip, torch.Tensor) or flip.device.type != "cpu" or flip.dtype not in (torch.bool, torch.uint8)
+                    or tuple(flip.shape) != (b,)):
+                raise ValueError(f"flip must be a CPU bool or uint8 tensor [{b}], one flag per clip, got "
+                                 f"{getattr(flip, 'dtype', type(flip))} {tuple(getattr(flip, 'shape', ()))}")
+            flip = flip.ne(0).to(torch.uint8)
+        return boxes, flip
+
+    def batch(self, indices, *, attn_diff=False, out=None, boxes=None, flip=None, frame_norm=True):
         """The clips `indices` (a CPU sequence or integer tensor; duplicates allowed; anything outside [0, len) raises before any device
         work) -> (attn [B,1,clip_frames,S,S] f32, audio [B, clip_samples] f32) on the current stream.  out=(attn, audio): buffers of
         those shapes to fill (attn contiguous; audio with unit last stride, its rows may be longer than a clip).  The start tables
-        reach the device in one copy from pinned memory: no synchronisation."""
-        return self.cut(*self.check_indices(indices), attn_diff=attn_diff, out=out)
+        reach the device in one copy from pinned memory: no synchronisation.
 
-    def cut(self, frame_start, sample_start, *, attn_diff=False, out=None):
+        boxes= (CPU int32 [B, 4] of (top, left, height, width) in pixels of the S x S frame, as VideoTransform.sample_boxes and
+        BankCrop.sample give them) and / or flip= (CPU bool or uint8 [B]): every clip's stored maps are resampled from its box to the
+        whole patch grid and mirrored where flagged (maavss_bank_warp_maps; the definition is in include/maavss.h), each frame divided
+        by its own maximum again (frame_norm=True, as the extractor leaves it) or not, and the clip maximum, attn_diff and the x8
+        upsampling follow on the warped maps as they do on the stored ones.  Needs S % 8 == 0.  This crops the attention MAP: it is a
+        geometric augmentation of the tensor the fusion network reads, not the attention of the cropped frame (the ViT would attend
+        differently).  A frame whose box holds only zeros becomes NaN under frame_norm, as an all-zero map does in the extractor.
+        Every refusal is raised before any device work; boxes and flags travel in the same pinned copy as the start tables.  Without
+        boxes= and flip= the launches, buffers and bytes are those of the plain cut."""
+        starts = self.check_indices(indices)
+        return self.cut(*starts, attn_diff=attn_diff, out=out, boxes=boxes, flip=flip, frame_norm=frame_norm)
+
+    def _stage(self, frame_start, sample_start, warp):
+        """Every table of one batch in one non-blocking copy through pinned memory -> device int32: the int64 sample starts (8-byte
+        aligned) [0, 2b), the frame starts [2b, 3b) and, with a warp, the warped workspace's clip starts b * clip_frames [3b, 4b),
+        the boxes [4b, 8b) and the flip bytes [8b, ...)."""
+        b = frame_start.numel()
+        parts = [sample_start.view(torch.int32), frame_start]
+        if warp is not None:
+            flips = torch.zeros((b + 3) // 4 * 4, dtype=torch.uint8)
+            flips[:b] = warp[1]
+            parts += [torch.arange(b, dtype=torch.int32) * self.clip_frames, warp[0].reshape(-1), flips.view(torch.int32)]
+        host = torch.cat(parts)
+        staged = torch.empty(host.numel(), device=self.device, dtype=torch.int32)
+        staged.copy_(host.pin_memory(), non_blocking=True)
+        return staged
+
+    def _warp(self, staged, b, frame_norm):
+        """maavss_bank_warp_maps on the staged tables -> the workspace [b * clip_frames, frame_elems] f32."""
+        ws = torch.empty(b * self.clip_frames, self.frame_elems, device=self.device, dtype=torch.float32)
+        call("maavss_bank_warp_maps", ptr(self.maps), _STORAGE[self.storage][0], ptr(staged[2 * b:]), ptr(staged[4 * b:]), ptr(staged[8 * b:]),
+             b, self.n_frames, self.clip_frames, self.frame_size, int(bool(frame_norm)), ptr(ws), stream_ptr())
+        return ws
+
+    def warp_maps(self, indices, boxes, flip=None, frame_norm=True):
+        """The cropped / flipped maps batch(indices, boxes=, flip=, frame_norm=) upsamples, at patch resolution -> f32
+        [B, clip_frames, S // 8, S // 8] on the current stream; one launch, no synchronisation."""
+        frame_start, sample_start = self.check_indices(indices)
+        b = frame_start.numel()
+        if boxes is None:
+            raise ValueError("warp_maps needs boxes=")
+        warp = self.check_warp(b, boxes, flip, frame_norm)
+        _lib.require_cuda(self.maps)
+        ws = self._warp(self._stage(frame_start, sample_start, warp), b, frame_norm)
+        return ws.view(b, self.clip_frames, self.frame_size // 8, self.frame_size // 8)
+
+    def cut(self, frame_start, sample_start, *, attn_diff=False, out=None, boxes=None, flip=None, frame_norm=True):
         """batch() behind its index check: the two CPU tables check_indices returned -> (attn, audio)."""
         b, t, s, n =frame_start.numel(), self.clip_frames, self.frame_size, self.clip_samples
+        warp = self.check_warp(b, boxes, flip, frame_norm)
         if out is None:
             _lib.require_cuda(self.maps)
             attn = torch.empty(b, 1, t, s, s, device=self.device, dtype=torch.float32)
@@ -257,15 +341,18 @@ class ClipBank:
                 raise ValueError(f"out[1] must be a float32 {[b, n]} tensor with unit last stride and rows that do not overlap, got "
                                  f"{getattr(audio, 'dtype', type(audio))} {tuple(getattr(audio, 'shape', ()))}")
             _lib.require_cuda(self.maps, attn, audio)
-        # both tables in one copy through pinned memory, as Mixer stages its partners: a blocking copy on ClipPipeline's side stream would
-        # hold the host until the work queued in front of it had finished.  int64 sample starts first (8-byte aligned), then the frames
-        host = torch.cat([sample_start.view(torch.int32), frame_start])
-        staged = torch.empty(3 * b, device=self.device, dtype=torch.int32)
-        staged.copy_(host.pin_memory(), non_blocking=True)
+        # every table in one copy through pinned memory, as Mixer stages its partners: a blocking copy on ClipPipeline's side stream would
+        # hold the host until the work queued in front of it had finished
+        staged = self._stage(frame_start, sample_start, warp)
         rcp = torch.empty(b, device=self.device, dtype=torch.float32)
         st = stream_ptr()
-        call("maavss_bank_attn_clips", ptr(self.maps), _STORAGE[self.storage][0], ptr(staged[2 * b:]), b, self.n_frames, t, s, s,
-             int(bool(attn_diff)), ptr(rcp), ptr(attn), st)
+        if warp is None:
+            call("maavss_bank_attn_clips", ptr(self.maps), _STORAGE[self.storage][0], ptr(staged[2 * b:]), b, self.n_frames, t, s, s,
+                 int(bool(attn_diff)), ptr(rcp), ptr(attn), st)
+        else:
+            # the warped maps are an f32 bank of b clips laid end to end: the clip maximum and the x8 stores are the plain cut's
+            ws = self._warp(staged, b, frame_norm)
+            call("maavss_bank_attn_clips", ptr(ws), 0, ptr(staged[3 * b:]), b, b * t, t, s, s, int(bool(attn_diff)), ptr(rcp), ptr(attn), st)
         call("maavss_bank_audio_clips", ptr(self.audio), self.n_samples, ptr(staged), b, n, ptr(audio), audio.stride(0) if b > 1 else n, st)
         return attn, audio
 
@@ -371,3 +458,29 @@ class ClipBank:
         bank.maps[:bank.n_frames].copy_(maps[:bank.n_frames])
         bank.audio[:bank.n_samples].copy_(audio[:bank.n_samples])
         return bank
+
+
+class BankCrop:
+    """The random boxes and flips of ClipBank.batch(boxes=, flip=): `boxes, flip = BankCrop(scale, ratio, flip=p).sample(B, S, generator)`.
+
+    Host code.  Draw order: first the B boxes, exactly VideoTransform(S, scale, ratio).sample_boxes(B, S, S, generator) -- the
+    frames-fed path's RandomResizedCrop boxes on the S x S frame -- then, only when flip > 0, one torch.rand(B, dtype=float64,
+    generator=generator) < flip.  With flip == 0 the generator is left where the boxes left it and no clip is flipped."""
+
+    def __init__(self, scale=(0.6, 1.0), ratio=(3 / 4, 4 / 3), flip=0.0):
+        if not (0 < scale[0] <= scale[1]) or not (0 < ratio[0] <= ratio[1]):
+            raise ValueError(f"bad scale {scale} or ratio {ratio}")
+        if isinstance(flip, bool) or not isinstance(flip, (int, float)) or not 0.0 <= flip <= 1.0:
+            raise ValueError(f"flip must be a probability in [0, 1], got {flip!r}")
+        self.scale, self.ratio, self.flip = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1])), float(flip)
+
+    def sample(self, batch, frame_size, generator=None):
+        """-> (boxes CPU int32 [batch, 4] of (top, left, height, width), flip CPU bool [batch])."""
+        _positive_int("batch", batch)
+        s = _positive_int("frame_size", frame_size)
+        boxes = VideoTransform(s, self.scale, self.ratio).sample_boxes(batch, s, s, generator)
+        if self.flip > 0:
+            flip = torch.rand(batch, dtype=torch.float64, generator=generator) < self.flip
+        else:
+            flip = torch.zeros(batch, dtype=torch.bool)
+        return boxes, flip

@@ -17,7 +17,8 @@ With `mixer` (a Mixer built on the same STFT) the bare STFT call becomes the mix
 (the interferers are the clips after the audio transform), y stays the clip's own STFT.
 With `bank` (a ClipBank) the batches come from attention maps and audio already resident on the device: `submit_clips(indices, seed)`
 cuts them on the side stream (no ViT, no frame or audio transform) in front of the same STFT / mixer call; `video_attention` may
-then be None.
+then be None.  With `bank_crop` (a BankCrop) every clip of such a batch gets a random box and flip, and the bank cuts the batch through
+them (ClipBank.batch(boxes=, flip=): the stored maps cropped and mirrored, no ViT).
 With `reverb` (a Reverb holding a table of room responses) every clip is convolved with a room on the side stream in front of that
 call: from zero state in submit(), from its recording's past in the bank in submit_clips().  reverb_target="wet": the wet clips take
 the place of the audio, so y is reverberant too and every interferer of a mixture carries its own room; "dry": x is the STFT of the
@@ -30,14 +31,19 @@ from .reverb import bank_floor
 
 class ClipPipeline:
     def __init__(self, video_attention, stft, clip_frames, depth=2, finite_check="deferred", *, transform=None, audio_transform=None,
-                 audio_length=None, mixer=None, bank=None, reverb=None, reverb_target="wet"):
+                 audio_length=None, mixer=None, bank=None, reverb=None, reverb_target="wet", bank_crop=None):
         self.va, self.stft, self.t = video_attention, stft, clip_frames
         if bank is not None:
             if transform is not None or audio_transform is not None:
                 raise ValueError("transform= / audio_transform= do not go with bank=: a bank holds maps and audio that are already transformed")
             if bank.clip_frames != clip_frames:
                 raise ValueError(f"the bank cuts clips of {bank.clip_frames} frames, the pipeline was given clip_frames={clip_frames}")
-        self.bank = bank
+        if bank_crop is not None:
+            if bank is None:
+                raise ValueError("bank_crop= draws the crops of a bank's batches: it needs bank=")
+            if bank.frame_size % 8:
+                raise ValueError(f"bank_crop= needs a bank with frame_size % 8 == 0, got {bank.frame_size}")
+        self.bank, self.bank_crop = bank, bank_crop
         self.transform = transform
         if audio_transform is None and audio_length is not None:
             raise ValueError("audio_length needs a ClipPipeline built with audio_transform=")
@@ -171,11 +177,27 @@ class ClipPipeline:
             slot["ready"].record(self.side)
         self.head += 1
 
-    def submit_clips(self, indices, seed, *, attn_diff=False, partners=None, snr_db=None, rir_index=None):
+    def check_crop(self, b, seed, boxes, flip):
+        """Host-side validation / seeded draw of submit_clips()'s crops (no device work) -> (boxes, flip) for bank.cut, (None, None)
+        when there is nothing to warp."""
+        if self.bank_crop is None:
+            if boxes is not None or flip is not None:
+                raise ValueError("boxes / flip need a ClipPipeline built with bank_crop=")
+            return None, None
+        if boxes is None or flip is None:
+            drawn = self.bank_crop.sample(b, self.bank.frame_size, torch.Generator().manual_seed(seed))
+            boxes = drawn[0] if boxes is None else boxes
+            flip = drawn[1] if flip is None else flip
+        return self.bank.check_warp(b, boxes, flip)
+
+    def submit_clips(self, indices, seed, boxes=None, flip=None, *, attn_diff=False, partners=None, snr_db=None, rir_index=None):
         """Enqueue one batch cut from the bank: `indices` as ClipBank.batch takes them (CPU; checked before any device work), `seed`,
         `partners` and `snr_db` as in submit().  On the side stream bank.batch fills the slot's buffers, then the STFT / mixer call and
         the events are those of submit(); get() / release() do not change.  With a reverb the wet clips are reverb.bank_clips(bank, indices,
-        rir_index): convolved from bank.audio, each clip with its recording's past."""
+        rir_index): convolved from bank.audio, each clip with its recording's past.
+        With a bank_crop, `boxes` [B,4] int32 and `flip` [B] bool (CPU) crop and mirror each clip's maps; by default
+        bank_crop.sample(B, bank.frame_size, torch.Generator().manual_seed(seed)), which is what a serial
+        bank.batch(indices, boxes=, flip=) with that draw sees: a pipelined and a serial run get the same crops."""
         if self.bank is None:
             raise ValueError("submit_clips needs a ClipPipeline built with bank=")
         assert self.head - self.tail < self.depth, "pipeline full: get()/release() a batch first"
@@ -188,6 +210,7 @@ class ClipPipeline:
         if self.reverb is not None:
             self.reverb.check_bank(bank, b, rir_index, seed)
             floor = bank_floor(bank, indices)
+        boxes, flip = self.check_crop(b, seed, boxes, flip)
         f, s = b * self.t, bank.frame_size
         main = torch.cuda.current_stream()
         produced = torch.cuda.Event()
@@ -200,7 +223,7 @@ class ClipPipeline:
                 slot["attn"] = torch.empty(f, 1, s, s, device=bank.device, dtype=torch.float32)
             if slot.get("clips") is None or slot["clips"].shape != (b, bank.clip_samples):
                 slot["clips"] = torch.empty(b, bank.clip_samples, device=bank.device, dtype=torch.float32)
-            _, audio = bank.cut(*starts, attn_diff=attn_diff, out=(slot["attn"].view(b, 1, self.t, s, s), slot["clips"]))
+            _, audio = bank.cut(*starts, attn_diff=attn_diff, out=(slot["attn"].view(b, 1, self.t, s, s), slot["clips"]), boxes=boxes, flip=flip)
             wet = None if self.reverb is None else self.reverb.cut(bank, starts[1], floor, rir_index)
             self._encode(slot, audio, wet, partners, snr_db, seed)
             slot["ready"].record(self.side)
