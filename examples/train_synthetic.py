@@ -32,6 +32,8 @@ stream (ClipPipeline).
                                                                               # (maavss_amd.CallbackFigures: train_avse_frames.py:191-215)
     python examples/train_synthetic.py --audio_loss compressed [--compress 0.3 --loss_mix 0.3]    # the power-law compressed spectral loss
                                                                               # as the audio term (goes with --val, --mix and --overfit)
+    python examples/train_synthetic.py --wave_loss si_sdr [--wave_weight 0.1]  # the clip-level SI-SDR (or snr) of the inverse STFT of the
+                                                                              # joined windows, added to the objective (maavss_amd.WaveformLoss)
     python examples/train_synthetic.py --weight_decay 0.01 --ema 0.99 --skip_nonfinite --warmup 3 --schedule cosine [--val 2]
                                                                               # AdamW decay, averaged weights, the non-finite skip and a
                                                                               # warm-up + cosine rate (FusedAdam / maavss_amd.LRSchedule);
@@ -109,6 +111,10 @@ def main():
     ap.add_argument("--compress", type=float, default=0.3, metavar="C", help="with --audio_loss compressed: the exponent, in (0, 1]")
     ap.add_argument("--loss_mix", type=float, default=0.3, metavar="L",
                     help="with --audio_loss compressed: the weight of the complex term, in [0, 1]; the magnitude term gets 1 - L")
+    ap.add_argument("--wave_loss", choices=("si_sdr", "snr"), default=None,
+                    help="add the clip-level waveform loss of the inverse STFT of the num_seq windows' joined outputs "
+                         "(maavss_amd.WaveformLoss: TrainStep(wave_loss=...))")
+    ap.add_argument("--wave_weight", type=float, default=1.0, metavar="W", help="with --wave_loss: its weight in the objective (dB per unit)")
     ap.add_argument("--figures-dir", default="figures", metavar="D", help="with --figures: where the PNGs go")
     ap.add_argument("--weight_decay", type=float, default=0.0, metavar="W", help="AdamW's decoupled decay on the tensors with two or more dimensions")
     ap.add_argument("--ema", type=float, default=None, metavar="D",
@@ -153,7 +159,8 @@ def main():
                                          kind=a.schedule)
     step = maavss_amd.TrainStep(model, lr=schedule if schedule is not None else a.lr, loss_coeff=0.001, num_seq=ns, max_grad_norm=a.clip,
                                 audio_loss=audio_loss, weight_decay=a.weight_decay, ema_decay=a.ema, ema_warmup=a.ema is not None,
-                                skip_nonfinite=a.skip_nonfinite)
+                                skip_nonfinite=a.skip_nonfinite,
+                                wave_loss=maavss_amd.WaveformLoss(stft, kind=a.wave_loss) if a.wave_loss else None, wave_weight=a.wave_weight)
     watch = maavss_amd.ModelWatch(step, log_freq=a.watch) if a.watch else None
     figures = maavss_amd.CallbackFigures(stft) if a.figures else None
     transform = None
@@ -337,7 +344,8 @@ def main():
             parts = "" if audio_loss is None else "  (magnitude {:.5f}, complex {:.5f})".format(*step.loss_parts.tolist())
             rate = "" if schedule is None else f"  lr {step.opt.lr:.3g}"
             skips = "" if not a.skip_nonfinite else f"  skipped {step.opt.skipped_steps.item()}"
-            print(f"step {i}: a_loss {losses[0].item():.5f}{parts}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{clip}{rate}{skips}",
+            wave = "" if not a.wave_loss else f"  {a.wave_loss} loss {step.wave['loss'].item():.3f} dB"
+            print(f"step {i}: a_loss {losses[0].item():.5f}{parts}  v_loss {losses[1].item():.5f}  loss {losses[2].item():.5f}{wave}{clip}{rate}{skips}",
                   flush=True)
         if validator is not None and (i + 1) % a.val == 0:
             attn_v, x_v_stft, y_v_stft = held_out

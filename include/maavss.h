@@ -442,6 +442,38 @@ int maavss_spectral_loss_pair(const float* a_pred, const float* a_tgt, int64_t B
                               double eps, const float* v_pred, const float* v_tgt, int64_t nv, float coeff, float inv_num_seq, float* d_a,
                               float* d_v, float* losses, double* parts, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- EXTENSION: clip-level waveform loss through the inverse STFT (maavss_amd.WaveformLoss, TrainStep(wave_loss=...)) -----------
+ * SI-SDR or SNR of istft(pred) against istft(tgt), in dB with the sign of a loss (lower is better), and its gradient with respect to
+ * pred.  Added without a version bump.  tests/wave_loss_twin.py is the float64 restatement.  pred, tgt: f32 contiguous [B][2][T][F],
+ * F = n_bins = N/2 + 1 or N/2 (trimmed), N = n_fft in {256, 512, 1024}, T >= 2, 0 < hop <= N: the conditions of maavss_istft.
+ * window = the synthesis window w of maavss_istft.  L = hop (T - 1), c = (normalized ? sqrt N : 1) / N.
+ *   waves     x = istft(pred), s = istft(tgt), f32 [B][L], by maavss_istft's own kernels: bit-identical to what that entry returns
+ *   sums      Sxx = sum x^2, Sss = sum s^2, Sxs = sum x s, D = sum (x - s)^2: f64 sums over the exactly converted f32 samples in a
+ *             fixed order, the chunk passes of maavss_wave_metrics.  No mean is subtracted.
+ *   snr       kind 1: l = 10 log10(D + eps) - 10 log10(Sss + eps), E = D
+ *   si_sdr    kind 0: alpha = Sxs / (Sss + eps), E = sum (x - alpha s)^2 summed directly in a second pass,
+ *             l = 10 log10(E + eps) - 10 log10(alpha^2 Sss + eps)
+ *   rows      [B][5] f64 = (l, Sxx, Sss, Sxs, E).  eps > 0: every finite input has a finite loss and gradient; a row with a NaN or an
+ *             infinity in either wave has five NaNs and a NaN gradient, and no other row is touched.
+ *   gradient  g[n] = d(sum_b l_b) / dx[n] = a_b x[n] + b_b s[n] with k = 10 / ln 10:
+ *             snr      a = 2 k / (D + eps), b = -a
+ *             si_sdr   a = 2 k / (E + eps), b = -2 k alpha ((1 + eps / (Sss + eps)) / (E + eps) + Sss / ((Sss + eps) (alpha^2 Sss + eps)))
+ *             carried to the STFT planes by the adjoint of maavss_istft: den[p] = sum_t w[p - t hop]^2 over the frames that cover
+ *             position p of the centre-padded signal; u[p] = g[p - N/2] / den[p] for N/2 <= p < N/2 + L and 0 elsewhere;
+ *             q_t[j] = c w[j] u[t hop + j] (formed in f64, rounded once to f32);
+ *             d/dRe X_t[k] = grad_scale m_k sum_j q_t[j] cos(2 pi j k / N), d/dIm X_t[k] = -grad_scale m_k sum_j q_t[j] sin(2 pi j k / N),
+ *             m_k = 2 for 0 < k < N/2 and 1 for k = 0, N/2; the imaginary gradients of DC and Nyquist are 0 (irfft drops those inputs).
+ * d_pred (nullable: the forward-only form writes no gradient): block t / d_frames of the destination takes frame t of the clip; a block
+ * is a contiguous [B][2][d_frames][F] and blocks lie d_block_stride elements apart (d_frames = T: one block, pred's own layout;
+ * d_frames must divide T).  accumulate != 0 adds the gradient, rounded to f32, to what the destination holds.
+ * ws: maavss_wave_loss_ws_bytes(B, T, n_fft, hop) bytes, 8-byte aligned; 0 for invalid sizes.  It starts with the two waves,
+ * x [B][L] then s [B][L] f32, followed by the iSTFT frame buffer, the envelope and the chunk partials.  No floating-point atomics: two
+ * runs give identical bytes.  Launches only; nothing waits for the device. */
+int64_t maavss_wave_loss_ws_bytes(int64_t B, int64_t T, int n_fft, int hop);
+int maavss_wave_loss(const float* pred, const float* tgt, int64_t B, int64_t T, int n_bins, const float* window, int n_fft, int hop,
+                     int normalized, int kind, double eps, double grad_scale, float* d_pred, int64_t d_frames, int64_t d_block_stride,
+                     int accumulate, double* rows, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- EXTENSION: intelligibility scores (maavss_amd.stoi_metrics, Validator(intelligibility_sr=...)) -----------------------------
  * maavss_stoi: short-time objective intelligibility (STOI, Taal et al. 2011) and its extended form (ESTOI, Jensen & Taal 2016) of est
  * [rows][n] against ref [rows][n], f32 sampled at 10 kHz, per row.  Samples are widened to f64 on load and every operation from there on is

@@ -23,6 +23,7 @@ from .quality import Validator, plan_wave_chunks, spectrum_metrics, wave_metrics
 from .stoi import stoi_metrics  # noqa: F401
 from .bss import bss_eval_metrics  # noqa: F401
 from .spectral_loss import SpectralLoss  # noqa: F401
+from .wave_loss import WaveformLoss  # noqa: F401
 from .clip_bank import BankCrop, ClipBank  # noqa: F401
 from .sampler import ClipSampler  # noqa: F401
 from .figures import (CallbackFigures, filmstrip_image, save_png, specgram_images, specgram_planes, stft_panels,  # noqa: F401

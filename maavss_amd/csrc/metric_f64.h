@@ -34,6 +34,17 @@ __device__ __forceinline__ void fft2_rotate_add(double* zr, double* zi, int i0, 
 // k < K in index order (wave_strided_sum_d), column 1 divided by div1 (1.0 leaves the sum's bits).  -> a status
 int rows_sum_launch(const double* partials, int64_t rows, int64_t per_row, int K, double div1, double* out, hipStream_t st);
 
+// quality_metrics.hip: the two chunk passes of the wave metrics, for wave_loss.hip.  A row of L samples is cut into
+// wave_chunks_per_row(L, seg_len) chunks, one workgroup each.  wave_sums_launch: per chunk WAVE_PARTIAL_DOUBLES doubles
+// {sum ref^2, sum est^2, sum ref est, sum (est - ref)^2, segmental sum, frames}; wave_scaled_sqerr_launch: per chunk
+// sum (est - alpha[row] ref)^2.  A row's partials are added in index order (wave_strided_sum_d).  -> a status
+#define WAVE_PARTIAL_DOUBLES 6
+int64_t wave_chunks_per_row(int64_t L, int seg_len);
+int wave_sums_launch(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L, int seg_len,
+                     void* partials, hipStream_t st);
+int wave_scaled_sqerr_launch(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L, int seg_len,
+                             const double* alpha, double* partials, hipStream_t st);
+
 // the checks an entry makes of est [rows][n], ref [rows][n] (f32, row strides in elements), out and its workspace (f64); `who`
 // names the entry in the message.  The stride of a single row is not looked at: the entry passes 0 to its kernels then.
 static inline int metric_rows_check(const char* who, const void* est, int64_t est_stride, const void* ref, int64_t ref_stride, int64_t rows,

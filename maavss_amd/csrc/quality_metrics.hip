@@ -252,6 +252,29 @@ int rows_sum_launch(const double* partials, int64_t rows, int64_t per_row, int K
   return MAAVSS_OK;
 }
 
+// The two chunk passes of the wave metrics, also launched by wave_loss.hip (metric_f64.h): one copy of the sums.
+int64_t wave_chunks_per_row(int64_t L, int seg_len) { return wm_chunks_per_row(L, seg_len); }
+
+int wave_sums_launch(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L, int seg_len,
+                     void* partials, hipStream_t st) {
+  int G = 1;
+  while (G < seg_len && G < 64) G <<= 1;
+  const int64_t nch = wm_chunks_per_row(L, seg_len);
+  hipLaunchKernelGGL(wave_metrics_pass1_kernel, dim3((unsigned)(B * nch)), dim3(256), 0, st, est, est_stride, ref, ref_stride, L, seg_len,
+                     wm_chunk_len(seg_len), nch, G, (wm_partial*)partials);
+  MAAVSS_LAUNCH_CHECK("wave_metrics_pass1_kernel");
+  return MAAVSS_OK;
+}
+
+int wave_scaled_sqerr_launch(const float* est, int64_t est_stride, const float* ref, int64_t ref_stride, int64_t B, int64_t L, int seg_len,
+                             const double* alpha, double* partials, hipStream_t st) {
+  const int64_t nch = wm_chunks_per_row(L, seg_len);
+  hipLaunchKernelGGL(sqerr_scaled_chunks_kernel<true>, dim3((unsigned)(B * nch)), dim3(256), 0, st, est, est_stride, ref, ref_stride, L,
+                     wm_chunk_len(seg_len), nch, alpha, partials);
+  MAAVSS_LAUNCH_CHECK("sqerr_scaled_chunks_kernel");
+  return MAAVSS_OK;
+}
+
 extern "C" int maavss_wave_metrics_chunk(void) { return WM_CH; }
 
 extern "C" int64_t maavss_wave_metrics_ws_bytes(int64_t B, int64_t L, int seg_len) {
@@ -275,16 +298,11 @@ extern "C" int maavss_wave_metrics(const float* est, int64_t est_stride, const f
   wm_partial* partials = (wm_partial*)ws;
   double* srr = (double*)((char*)ws + align256(B * nch * (int64_t)sizeof(wm_partial)));
   double* alpha = (double*)((char*)srr + align256(B * nch * 8));
-  int G = 1;
-  while (G < seg_len && G < 64) G <<= 1;
-  const int cl = wm_chunk_len(seg_len);
   const int64_t es = B == 1 ? 0 : est_stride, rs = B == 1 ? 0 : ref_stride;
-  hipLaunchKernelGGL(wave_metrics_pass1_kernel, dim3((unsigned)(B * nch)), dim3(256), 0, st, est, es, ref, rs, L, seg_len, cl, nch, G, partials);
-  MAAVSS_LAUNCH_CHECK("wave_metrics_pass1_kernel");
+  if (int rc = wave_sums_launch(est, es, ref, rs, B, L, seg_len, partials, st)) return rc;
   hipLaunchKernelGGL(wave_metrics_finalize1_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, nch, alpha, out);
   MAAVSS_LAUNCH_CHECK("wave_metrics_finalize1_kernel");
-  hipLaunchKernelGGL(sqerr_scaled_chunks_kernel<true>, dim3((unsigned)(B * nch)), dim3(256), 0, st, est, es, ref, rs, L, cl, nch, alpha, srr);
-  MAAVSS_LAUNCH_CHECK("sqerr_scaled_chunks_kernel");
+  if (int rc = wave_scaled_sqerr_launch(est, es, ref, rs, B, L, seg_len, alpha, srr, st)) return rc;
   hipLaunchKernelGGL(wave_metrics_finalize2_kernel, dim3((unsigned)B), dim3(64), 0, st, srr, nch, alpha, out);
   MAAVSS_LAUNCH_CHECK("wave_metrics_finalize2_kernel");
   return MAAVSS_OK;

@@ -483,12 +483,21 @@ def act_bwd(dout, out, act):
     return dz
 
 
-def mse_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, num_seq=1, want_grads=True):
+def _d_a_buffer(a_pred, want_grads, d_a):
+    """The audio gradient's buffer: a fresh one, or the caller's `d_a` (f32, contiguous, a_pred's shape: TrainStep keeps the windows of
+    a clip in one allocation so that the clip's waveform gradient can be added to all of them by one launch)."""
+    if d_a is None:
+        return torch.empty_like(a_pred) if want_grads else None
+    assert want_grads and d_a.shape == a_pred.shape and d_a.dtype == torch.float32 and d_a.is_contiguous() and d_a.device == a_pred.device
+    return d_a
+
+
+def mse_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, num_seq=1, want_grads=True, d_a=None):
     """-> losses [3] (a_loss, v_loss, total) and d(total)/d(a_pred), d(total)/d(v_pred)."""
     _f32(a_pred, a_tgt, v_pred, v_tgt)
     assert a_pred.shape == a_tgt.shape and v_pred.shape == v_tgt.shape
     dev = a_pred.device
-    d_a = torch.empty_like(a_pred) if want_grads else None
+    d_a = _d_a_buffer(a_pred, want_grads, d_a)
     d_v = torch.empty_like(v_pred) if want_grads else None
     losses = torch.empty(3, device=dev, dtype=torch.float32)
     ws = torch.empty(1024, device=dev, dtype=torch.float32)
@@ -497,14 +506,14 @@ def mse_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, num_seq=1, want_grads=True):
     return losses, d_a, d_v
 
 
-def spectral_loss_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, loss, num_seq=1, want_grads=True):
+def spectral_loss_pair(a_pred, a_tgt, v_pred, v_tgt, coeff, loss, num_seq=1, want_grads=True, d_a=None):
     """mse_pair with the audio term replaced by `loss` (a maavss_amd.SpectralLoss) -> losses [3] in mse_pair's positions, d_a, d_v and
     parts f64 [2] = the magnitude and the complex mean that losses[0] mixes.  losses[1] and d_v are mse_pair's, bit for bit."""
     _f32(a_pred, a_tgt, v_pred, v_tgt)
     assert a_pred.shape == a_tgt.shape and v_pred.shape == v_tgt.shape and a_pred.dim() == 4 and a_pred.shape[1] == 2
     dev = a_pred.device
     b, _, t, f = a_pred.shape
-    d_a = torch.empty_like(a_pred) if want_grads else None
+    d_a = _d_a_buffer(a_pred, want_grads, d_a)
     d_v = torch.empty_like(v_pred) if want_grads else None
     losses = torch.empty(3, device=dev, dtype=torch.float32)
     parts = torch.empty(2, device=dev, dtype=torch.float64)

@@ -19,10 +19,13 @@ does); the only mandatory collective is the gradient sum.  BatchNorm uses per-ra
 (as torch DDP does without SyncBatchNorm); `TrainStep(sync_bn=True)` all-reduces the per-channel sums instead,
 which reproduces the single-device reference on the concatenated batch -- documented in DESIGN.md.
 """
+import math
+
 import torch
 
 from . import ops
 from .spectral_loss import SpectralLoss
+from .wave_loss import WaveformLoss
 
 _FUSION_PREFIXES = ("lstm.", "fc1.", "fc2.", "a_fc1.", "v_fc1.")
 
@@ -570,7 +573,7 @@ class TrainStep:
 
     def __init__(self, model, lr=1e-5, loss_coeff=0.001, num_seq=1, betas=(0.9, 0.999), eps=1e-8,
                  process_group=None, sync_bn=False, grad_wire_dtype=None, max_grad_norm=None, audio_loss=None, weight_decay=0.0,
-                 decay_filter=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False):
+                 decay_filter=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False, wave_loss=None, wave_weight=1.0):
         """`audio_loss`: None trains on the reference's MSE of the STFT planes (ops.mse_pair); a maavss_amd.SpectralLoss replaces that
         term by the power-law compressed spectral loss (ops.spectral_loss_pair): `losses` keeps its three positions (losses[0] is the
         new audio loss, losses[1] the attention MSE by mse_pair's own kernel) and `loss_parts` holds the magnitude and the complex
@@ -580,7 +583,21 @@ class TrainStep:
         followed by clip_grad_norm_ gives; every rank computes it from identical bytes, so there is no extra collective.
         `lr` (a float or a maavss_amd.LRSchedule), `weight_decay`, `decay_filter`, `ema_decay`, `ema_warmup`, `skip_nonfinite`: FusedAdam's
         (not in the reference; all off by default).  The skip is decided from the same all-reduced gradient bytes on every rank, so the
-        ranks agree without a collective."""
+        ranks agree without a collective.
+        `wave_loss`: None, or a maavss_amd.WaveformLoss whose STFT has the model's n_bins.  sliding_window_step then adds
+        wave_weight times the mean over the batch of the clip's SI-SDR / SNR loss -- of the inverse STFT of the num_seq windows' joined
+        outputs against the joined targets -- to its objective; `wave` holds the evaluation (device f64: "rows" [B, 5], "loss").
+        wave_weight = 0 evaluates and reports the loss without adding its gradient.  The windows' backward passes then run after all
+        forwards, so num_seq sets of saved activations are alive at once (README.md has the measured peak)."""
+        if wave_loss is not None:
+            if not isinstance(wave_loss, WaveformLoss):
+                raise ValueError(f"wave_loss must be None or a maavss_amd.WaveformLoss, got {wave_loss!r}")
+            if wave_loss.stft.n_bins() != model.n_bins:
+                raise ValueError(f"wave_loss: its STFT has n_bins() = {wave_loss.stft.n_bins()}, the model has n_bins = {model.n_bins}")
+        if isinstance(wave_weight, bool) or not isinstance(wave_weight, (int, float)) or not math.isfinite(wave_weight) or wave_weight < 0:
+            raise ValueError(f"wave_weight must be a finite number >= 0, got {wave_weight!r}")
+        self.wave_loss, self.wave_weight = wave_loss, float(wave_weight)
+        self.wave = None
         self.model = model
         self.flat = FlatParams(model)
         self.opt = FusedAdam(self.flat, lr, betas, eps, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_filter=decay_filter,
@@ -603,6 +620,9 @@ class TrainStep:
         """One window: forward, loss / num_seq, backward.  `accumulate` adds into the flat gradient buffer instead of
         overwriting it; the gradient all-reduce and Adam run only when `last` (sliding_window_step drives both).
         requires_grad is read at every call (toggle_* between steps take effect, as with autograd)."""
+        if self.wave_loss is not None:
+            raise ValueError("with wave_loss set the step is sliding_window_step (the loss needs the whole clip; a single window is a clip "
+                             "of num_seq = 1 there)")
         m = self.model
         need = {n: bool(p.requires_grad) for n, p in m.named_parameters()}
         if not accumulate:
@@ -639,6 +659,8 @@ class TrainStep:
         (accumulated in the flat buffer); ONE gradient all-reduce and ONE Adam step follow.  Returns the last
         window's (a_loss, v_loss, loss) like the reference logs (:183-188) and, with `collect`, the stitched
         outputs (output_stft [B,2,hpf*num_seq,F], output_attn [B,1,num_seq,H,W]) of its callback (:150-176)."""
+        if self.wave_loss is not None:
+            return self._clip_step(x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, collect)
         ns = self.num_seq
         outs_a, outs_v = [], []
         for j, xa, xv, ya, yv in sliding_windows(x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, ns):
@@ -648,4 +670,52 @@ class TrainStep:
                 outs_v.append(self.outputs[1])
         if collect:
             return self.losses, torch.cat(outs_a, dim=2), torch.stack(outs_v, dim=2)
+        return self.losses
+
+    def _clip_step(self, x_stft, y_stft, x_attn, y_attn, num_frames, hops_per_frame, collect):
+        """sliding_window_step with `wave_loss`: the objective is (1 / num_seq) sum_j (a_loss_j + loss_coeff v_loss_j), what the step
+        optimises without it, plus wave_weight times the mean over the batch of the clip's waveform loss.  All forwards first (every
+        window keeps its saved state; BatchNorm's running statistics move once per window, as ever), then the loss of the joined
+        outputs [B,2,hpf*num_seq,F] against the joined targets, whose gradient the kernel adds to the windows' d_a, then the backwards
+        in window order; the gradient all-reduce and Adam run in the last one.  `losses` stays the last window's three numbers,
+        without the wave term."""
+        m, ns, hpf = self.model, self.num_seq, hops_per_frame
+        need = {n: bool(p.requires_grad) for n, p in m.named_parameters()}
+        self.flat.touched.clear()
+        saved, outs_a, outs_v, d_vs, d_all = [], [], [], [], None
+        for j, xa, xv, ya, yv in sliding_windows(x_stft, y_stft, x_attn, y_attn, num_frames, hpf, ns):
+            (a, v, fused), sv = m._engine_forward(xa, xv, train=True)
+            self.outputs = (a, v, fused)
+            if d_all is None:
+                d_all = torch.empty((ns,) + tuple(a.shape), device=a.device, dtype=torch.float32)      # the windows' d_a, one block each
+            if self.audio_loss is None:
+                self.losses, _, d_v = ops.mse_pair(a, ya.contiguous(), v, yv.contiguous(), self.loss_coeff, ns, d_a=d_all[j])
+            else:
+                self.losses, _, d_v, self.loss_parts = ops.spectral_loss_pair(a, ya.contiguous(), v, yv.contiguous(), self.loss_coeff,
+                                                                              self.audio_loss, ns, d_a=d_all[j])
+            saved.append(sv)
+            outs_a.append(a)
+            outs_v.append(v)
+            d_vs.append(d_v)
+        mid = (ns - 1) // 2
+        pred = torch.cat(outs_a, dim=2)
+        tgt = y_stft[:, :, hpf * mid:hpf * (mid + ns), :]
+        if self.wave_weight > 0.0:
+            res = self.wave_loss(pred, tgt, grad_scale=self.wave_weight / pred.shape[0], into=d_all)
+        else:
+            res = self.wave_loss(pred, tgt)
+        self.wave = {"rows": res["rows"], "loss": res["loss"]}
+        for j in range(ns):
+            last = j == ns - 1
+            if last:
+                self.sync.begin(n for n in m._param_names if need.get(n, False))
+            out = m._engine_backward(saved[j], d_all[j], d_vs[j], None, need, grads=self.flat.grad_views, accumulate=j > 0,
+                                     on_fusion_done=self.sync.start_fusion if last else None,
+                                     on_grad=self.sync.grad_ready if last else None)
+            saved[j] = None
+            self.flat.mark(out.keys())
+        self.sync.finish()
+        self.opt.step(grad_scale=1.0 / self.sync.world)
+        if collect:
+            return self.losses, pred, torch.stack(outs_v, dim=2)
         return self.losses
